@@ -10,6 +10,7 @@ host targets -> forward (conv/BN stack, corner map, GPU RoI proposal, RoI editin
 costs -> backward -> (N>1: RCCL gradient all-reduce overlapped with backward) -> fused nesterov update.
 Inputs are resident in HBM before the timed region. Rank 0 prints ONE JSON line. N > 1: key `data_parallel` (backend as the
 process group reports it, per-rank ms/step, all-reduce bytes and buckets per step, event-timed exposed collective time).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs), for comparing two builds.
 
 Extra legs (rank 0, N=1 only; outside the timed region):
   roofline      the dominant kernel (the matrix-kernel SYMBOL with the largest total time, named as rocprofv3 names it) is timed
@@ -393,6 +394,36 @@ def regime_leg(args, xd, metas, target_cells, lr, mom, decay):
                     "(regime_leg in bench.py says why)"}
 
 
+DUMP_SAMPLE = 1 << 21      # positions sampled from each long flat vector (8 MB in float32, the index 16 MB in float64)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, model, dns_layer, cost, costs):
+    """what a caller of the timed path received from its last step, as float32 / float64 .npy files (about 32 MB in all):
+    cost (the train_step return value), layer_costs (the per-layer costs it returns beside it), rois (the step's RoI list:
+    image, score, x0, y0, x1, y1 per row, float64 as the layer keeps it), params / momentum (the flat parameter and momentum
+    vectors after the update: all of them when they are short, else both at the same seeded DUMP_SAMPLE positions, ascending,
+    written as sample_index). Inputs, seeds and the sample are fixed, so two builds can be compared file by file."""
+    import numpy
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"cost": numpy.array([cost], dtype=numpy.float64),
+              "layer_costs": numpy.array([float(c) for c in costs], dtype=numpy.float64)}
+    rows = [numpy.column_stack([numpy.full(len(pr), b, dtype=numpy.float64), pr, boxes.reshape(-1, 4)])
+            for b, (pr, boxes) in enumerate(zip(dns_layer.sample_pr, dns_layer.sample_boxes))]
+    arrays["rois"] = numpy.concatenate(rows, axis=0) if rows else numpy.zeros((0, 6))
+    n = model.P.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = numpy.sort(numpy.random.RandomState(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        arrays["sample_index"] = idx.astype(numpy.float64)
+    for name, vec in (("params", model.P), ("momentum", model.M)):
+        host = vec.detach().cpu().numpy().astype(numpy.float32, copy=False)
+        arrays[name] = host if idx is None else host[idx]
+    for name, a in arrays.items():
+        numpy.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,7 +447,12 @@ def main():
                     help="LAUNCH-PATH DEBUG MODE, never a scaling measurement: all N ranks run on cuda:0 and torch.distributed "
                          "uses gloo (one GPU cannot host two RCCL ranks); exercises launcher, rendezvous, bucketed "
                          "all-reduce and the rank-0 JSON line on a one-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (costs, RoI list, seeded samples of the parameter and momentum "
+                         "vectors after the update) as DIR/<name>.npy, rank 0; see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)          # does not return
 
@@ -496,12 +532,14 @@ def main():
     try:              # of the shipped epoch loops too (ModelCNN.train_epoch / train_epoch_device: _collector_paused)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            cost, _ = model.train_step(xd, metas, 0, it, lr, mom, decay)
+            cost, costs = model.train_step(xd, metas, 0, it, lr, mom, decay)
             it += 1
         sync()
         dt_rank = dt = time.perf_counter() - t0
     finally:
         gc.enable()
+    # before any leg below trains the model further: the state the last timed step left
+    dumped = dump_outputs(args.dump_outputs, model, dns_layer, cost, costs) if args.dump_outputs and rank == 0 else None
     # what the corner detector did during the timed steps: as initialised it is silent (bias +5), but the corner cost (factor 100,
     # lr 0.1) has it firing within the warm-up steps and cooling down over the next ~30 - the timed steps see a detector that
     # proposes, and the RoI lists are trimmed by random.sample
@@ -571,6 +609,8 @@ def main():
 
     if dp_info is not None:
         out["data_parallel"] = dp_info
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
 
     # ---- self-audit: WHICH kernels the timed steps ran, layer by layer, and under which switches (one more step outside the
     # timed region; the C side notes the instantiation of every matrix-kernel launch, no events, no effect on streams) ----
