@@ -451,7 +451,7 @@ def _conv_wino_fwd_linked(link, g, tile, w, bias, add, out, cache, bn_stats):
         if st is None or st.numel() < nrows * 2 * K:
             st = cache["bn_stats_buf"] = torch.empty(nrows * 2 * K, dtype=torch.float64, device="cuda")
         cache["bn_stats"] = None
-    cache["fwd_tile"] = tile
+    _note_fwd_tile(cache, tile)
     u = _cached_u(cache, 0, tile)
     v_keep = None
     if _decided(2, g) == tile:               # the filter gradient of this layer reuses the transformed input
@@ -591,7 +591,7 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
     y = out if out is not None else empty(N, OH, OW, K)
     if add is None and not relu and _bf16x3_geom(g):
         if cache is not None:
-            cache["fwd_tile"] = 0
+            _note_fwd_tile(cache, 0)
             cache["bn_stats"] = None               # the batch norm behind measures its own statistics
         return _gemm_bf16x3(x, w, bias, y, N * H * W, K, C)
     _tune_first(0, g, x, w, bias, add, y, None)
@@ -623,7 +623,7 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
     # INFERENCE (no filter gradient will want the transformed input of this pass, the batch norms are folded into plain tensors):
     # the tuned file may name another algorithm for the forward pass alone - mode 3 entries (the tile-parallel fused F(4x4) kernel
     # on the many-channel layers, where training keeps the component-walk kernel because its V feeds the filter gradient)
-    if cache is not None and not cache.get("train") and (3, g) in _WINO and _tile_allowed(0, _WINO[(3, g)]):
+    if cache is not None and not cache.get("train") and (3, g) in _WINO and _tile_allowed(3, _WINO[(3, g)]):
         t3 = _WINO[(3, g)]
         if (t3 == FUSED4 and conv_wino4t_ok(0, g)) or (t3 in (2, 4) and conv_wino_ok(g, t3)) or t3 == 0:
             tile = t3
@@ -632,8 +632,10 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
             PROFILE.add(_conv_flops(g, logical) / _WINO_GAIN[tile])     # the FLOPs its batched GEMM really executes
         u = v_keep = None
         if cache is not None:
-            cache["fwd_tile"] = tile
-            u = _cached_u(cache, 0, tile)
+            _note_fwd_tile(cache, tile)
+            # filters prepared ahead by wino_prefetch_filters are those of a training step (unfolded weights, the training
+            # algorithm): an inference pass never takes them
+            u = _cached_u(cache, 0, tile) if cache.get("train") else None
             if u is None and not cache.get("train"):
                 # inference: the filters do not change between calls - transform them once per weights version
                 ent = cache.get("u_test")
@@ -654,7 +656,7 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
                              up=up)
     assert up is None
     if cache is not None:
-        cache["fwd_tile"] = 0
+        _note_fwd_tile(cache, 0)
     if PROFILE is not None:
         PROFILE.add(_conv_flops(g, logical))
     direct(final=True)
@@ -712,7 +714,8 @@ def _tile_allowed(mode, tile):
     if tile == FUSED2:
         return WINOGRAD >= 2 and mode in (0, 1, 2) and bool((WINO2F >> mode) & 1)
     if tile == FUSED4:
-        return WINOGRAD >= 4 and mode in (0, 1, 3) and bool((WINO4T >> (mode & 1)) & 1)       # (mode 3: the inference forward pass)
+        # DENET_WINO4T bit 0: the forward passes (mode 0, and mode 3, the inference forward pass); bit 1: the data gradient
+        return WINOGRAD >= 4 and mode in (0, 1, 3) and bool((WINO4T >> (1 if mode == 1 else 0)) & 1)
     return tile <= WINOGRAD
 
 
@@ -795,11 +798,19 @@ def _wino_tile(mode, g, direct, wino):
     return use
 
 
+def _note_fwd_tile(cache, tile):
+    """records the algorithm of a forward pass; a training pass's is the one wino_prefetch_filters prepares filters for (an
+    inference pass may run another one on the same layer: the mode-3 entries of the tuned file)"""
+    cache["fwd_tile"] = tile
+    if cache.get("train"):
+        cache["fwd_tile_train"] = tile
+
+
 def _cached_u(cache, dgrad, tile):
     """transformed filters prepared ahead by wino_prefetch_filters (None: the call transforms them itself)"""
     ent = cache.get(("u", dgrad))
-    if ent is None or ent[0] != tile or not ent[2]:
-        return None
+    if ent is None or ent[0] != tile or not ent[2] or ent[3] != WEIGHTS_VERSION:
+        return None                           # (prepared for another algorithm, taken already, or from weights since updated)
     wait_upload(cache.get(("u_event", dgrad)))
     ent[2] = False                            # valid for one step: the solver changes the weights
     return ent[1]
@@ -837,7 +848,7 @@ def wino_prefetch_filters(caches_and_weights, after=None):
     """For every convolution layer that runs Winograd passes: transform its filters for the forward and the data-gradient
     pass on a side stream, right at the start of a training step (the ~60 small launches leave the critical path)."""
     global _SIDE_FILTER
-    todo = [(c, w) for c, w in caches_and_weights if c.get("fwd_tile") or c.get("dgrad_tile")]
+    todo = [(c, w) for c, w in caches_and_weights if c.get("fwd_tile_train") or c.get("dgrad_tile")]
     tr = [(c, w) for c, w in caches_and_weights if c.get("dgrad_1x1t") or c.get("dgrad_t")]
     s2 = [(c, w) for c, w in caches_and_weights if c.get("dgrad_s2")]
     if not todo and not tr and not s2:
@@ -863,19 +874,21 @@ def wino_prefetch_filters(caches_and_weights, after=None):
                 ft = _filter_tile(tile)
                 if ent is None or ent[0] != tile:
                     K, _, _, C = w.shape
-                    ent = c[("u", dgrad)] = [tile, torch.empty((ft + 2) * (ft + 2) * K * C, dtype=torch.float32, device="cuda"), False]
+                    ent = c[("u", dgrad)] = [tile, torch.empty((ft + 2) * (ft + 2) * K * C, dtype=torch.float32, device="cuda"), False,
+                                             None]
                 if tile == FUSED4:
                     conv_wino4t_filter(w, dgrad, out=ent[1])
                 else:
                     conv_wino_filter(w, ft, dgrad, out=ent[1])
                 ent[2] = True
+                ent[3] = WEIGHTS_VERSION          # valid until the solver step that ends this training step changes the weights
             ev = torch.cuda.Event()
             ev.record(_SIDE_FILTER)
             for c, _ in items:
                 c[("u_event", dgrad)] = ev
         # forward filters in layer order, in groups of 8 layers; then the data-gradient filters (needed much later)
         for i in range(0, len(todo), 8):
-            run(todo[i:i + 8], 0, "fwd_tile")
+            run(todo[i:i + 8], 0, "fwd_tile_train")
         run(todo, 1, "dgrad_tile")
         if tr:
             # the transposed filters of the large 1x1 layers' data-gradient products (conv_dgrad)

@@ -178,3 +178,62 @@ def test_conv_passes_at_benchmark_geometry(hip, geom):
             assert mx <= bound, "%s %s %s (winograd tile %d): max-norm error %.2e > %.0e" % (name, label, p, wino, mx, bound)
             assert p999 <= 3 * bound, "%s %s %s: p99.9 element-wise error %.2e" % (name, label, p, p999)
             assert mx <= 1e-3 and p999 <= 1e-3                      # the north-star budget itself
+
+
+def _ref_fwd_fp64(x, w, pad):
+    """the fp64 forward correlation alone, in image chunks like _ref_fp64"""
+    B = x.shape[0]
+    w64 = w.double().permute(0, 3, 1, 2).contiguous()
+    step = max(1, min(B, (1 << 27) // x[0].numel()))
+    return torch.cat([Fn.conv2d(x[i:i + step].double().permute(0, 3, 1, 2), w64, None, padding=pad).permute(0, 2, 3, 1)
+                      for i in range(0, B, step)])
+
+
+def test_mode3_inference_entries_vs_fp64(hip):
+    """every MODE 3 entry of the committed tuned file (the inference forward pass alone - the batch-norm-folded test-mode pass of
+    get_detections at B = 32; training keeps its own mode-0 decision there) at its full geometry: conv_fwd in its inference form
+    (a layer cache without "train") with the three epilogues the folded pass runs - bias + ReLU (a convolution + `BN A` pair),
+    bias + residual add (a block's last convolution without ReLU) and bias + add + ReLU (resnet.py: forward_folded(add=res,
+    relu=True)) - runs the committed algorithm and agrees with an fp64 convolution to the F(4x4) bounds of this file (8e-5
+    max-norm, 2.4e-4 p99.9). The training forward pass at the same geometry is recorded beside it (key "train_fwd")."""
+    from denet_amd import ops
+    ops._load_tuned_once()
+    entries = sorted((g, t) for (m, g), t in ops._WINO.items() if m == 3)
+    assert entries, "the committed tuned file has no mode-3 entry"
+    for g, t3 in entries:
+        N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
+        name = "mode3_%dx%d_%d_%d" % (H, W, C, K)
+        gen = torch.Generator(device="cpu").manual_seed(H * 7 + C + 3 * K)
+        x = torch.randn(N, H, W, C, generator=gen).cuda()
+        w = (torch.randn(K, R, S, C, generator=gen) * (2.0 / (R * s_real * C)) ** 0.5).cuda()
+        bias = (0.5 * torch.randn(K, generator=gen)).cuda()
+        res_t = torch.randn(N, OH, OW, K, generator=gen).cuda()
+        assert ops.conv_geom(x.shape, w.shape, stride, pad, s_real) == g
+        r = _ref_fwd_fp64(x, w, pad)
+        rb = r + bias.double()
+        refs = {"bias_relu": (dict(bias=bias, relu=True), rb.clamp_min(0)),
+                "bias_add": (dict(bias=bias, add=res_t), rb + res_t.double()),
+                "bias_add_relu": (dict(bias=bias, add=res_t, relu=True), (rb + res_t.double()).clamp_min(0))}
+        del r
+        ent = {"algo": t3}
+        icache = {}
+        for label, (kw, ref) in refs.items():
+            y = ops.conv_fwd(x, w, stride=stride, pad=pad, s_real=s_real, cache=icache, **kw)
+            assert icache["fwd_tile"] == t3, (name, label, icache["fwd_tile"], t3)
+            ent[label] = _metrics(y, ref)
+            del y
+        y = ops.conv_fwd(x, w, stride=stride, pad=pad, s_real=s_real, bias=bias, add=res_t, relu=True)
+        ent["train_fwd"] = _metrics(y, refs["bias_add_relu"][1]) + (ops._WINO.get((0, g), 0),)
+        del y, refs
+        RESULTS[name] = ent
+        os.makedirs(os.path.dirname(OUT), exist_ok=True)
+        with open(OUT, "w") as f:
+            json.dump(RESULTS, f, indent=1)
+    for name, ent in RESULTS.items():
+        if not name.startswith("mode3_"):
+            continue
+        bound = {0: 1e-5, 2: 2e-5, 4: 8e-5, 22: 1e-5, 44: 8e-5}[ent["algo"]]
+        for label in ("bias_relu", "bias_add", "bias_add_relu"):
+            mx, p999 = ent[label]
+            assert mx <= bound, "%s %s (algorithm %d): max-norm error %.2e > %.0e (all: %s)" % (name, label, ent["algo"], mx, bound, ent)
+            assert p999 <= 3 * bound, "%s %s: p99.9 element-wise error %.2e (all: %s)" % (name, label, p999, ent)

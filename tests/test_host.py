@@ -878,3 +878,40 @@ def test_tune_merge_replaces_only_the_remeasured_keys():
     assert len(merged) == 6
     w = sorted(wkept + wadd)
     assert [0, geom(32, 64, 128), 4] in w and [1, geom(64, 56, 64), 22] in w and [0, geom(32, 16, 256), 4] in w and len(w) == 3
+
+
+@pytest.mark.parametrize("wino4t", [0, 1, 2, 3])
+def test_wino4t_switch_routes_the_inference_entries_by_the_forward_bit(monkeypatch, wino4t):
+    """DENET_WINO4T bit 0 is the forward bit, bit 1 the data-gradient bit (denet_amd/switches.py). The mode-3 entries of the tuned
+    file (the inference forward pass alone) are forward passes: load_tuned filters them and conv_fwd re-checks them with
+    _tile_allowed(3, ...), so the inference pass must follow bit 0 exactly like the training forward pass"""
+    from denet_amd import ops
+    monkeypatch.setattr(ops, "WINO4T", wino4t)
+    monkeypatch.setattr(ops, "WINOGRAD", 4)
+    assert ops._tile_allowed(3, ops.FUSED4) == ops._tile_allowed(0, ops.FUSED4) == bool(wino4t & 1)
+    assert ops._tile_allowed(1, ops.FUSED4) == bool(wino4t & 2)
+    assert not ops._tile_allowed(2, ops.FUSED4)
+
+
+def test_prefetched_filters_are_taken_by_the_step_that_prepared_them_only(monkeypatch):
+    """ops._cached_u hands out filters wino_prefetch_filters transformed at the start of a training step: for the algorithm they
+    were prepared for, once, and only while the weights they were transformed from are current (the solver step that ends
+    the training step bumps ops.WEIGHTS_VERSION). An inference pass on the same layer cache must never see them: conv_fwd asks
+    only when the cache is a training pass's, and the prefetch prepares the training pass's algorithm (fwd_tile_train), not the
+    last algorithm an inference pass ran (fwd_tile)"""
+    from denet_amd import ops
+    monkeypatch.setattr(ops, "WEIGHTS_VERSION", 7)
+    buf = object()
+    cache = {("u", 0): [4, buf, True, 7]}
+    assert ops._cached_u(cache, 0, ops.FUSED4) is None and cache[("u", 0)][2]      # another algorithm: not taken, not consumed
+    monkeypatch.setattr(ops, "WEIGHTS_VERSION", 8)
+    assert ops._cached_u(cache, 0, 4) is None                                       # the weights moved on: stale
+    monkeypatch.setattr(ops, "WEIGHTS_VERSION", 7)
+    assert ops._cached_u(cache, 0, 4) is buf
+    assert ops._cached_u(cache, 0, 4) is None                                       # once per step
+    # an inference pass records what it ran without changing what the training pass's prefetch prepares
+    c = {"train": True}
+    ops._note_fwd_tile(c, 4)
+    c["train"] = False
+    ops._note_fwd_tile(c, ops.FUSED4)
+    assert c["fwd_tile"] == ops.FUSED4 and c["fwd_tile_train"] == 4

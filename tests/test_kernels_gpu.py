@@ -243,13 +243,18 @@ def test_fused_winograd_f2_kernel(hip, case):
 
 
 @pytest.mark.parametrize("case", [(1, 8, 32, 64, 64), (2, 16, 64, 64, 64), (3, 12, 20, 64, 64), (2, 24, 40, 32, 128), (1, 16, 32, 128, 64),
-                                  (5, 64, 64, 64, 64), (2, 56, 56, 64, 64), (1, 4, 4, 32, 64)])
+                                  (5, 64, 64, 64, 64), (2, 56, 56, 64, 64), (1, 4, 4, 32, 64),
+                                  # the channel counts of the tuned file's mode-3 (inference) entries: (C, K) = (128, 128), (256, 128),
+                                  # (256, 256), (512, 256), on maps that are no multiple of the 8 x 32-pixel block
+                                  (1, 20, 36, 128, 128), (2, 12, 20, 256, 128), (2, 20, 44, 256, 256), (1, 8, 36, 512, 256)])
 def test_fused_winograd_f4_tile_parallel_kernel(hip, case):
     """csrc/wino4t.hip through ops (algorithm ops.FUSED4: input transform, 36 products, output transform in one launch) against an
     fp64 convolution: forward plain / with bias + add + batch-norm sums / with ReLU, and the data gradient with the accumulated add
     and with the backward sums of a batch norm (both mask forms). (3,12,20) and (2,56,56): maps that are no multiple of the
     8 x 32-pixel block (tiles masked, halo zero-filled); (2,24,40,32,128): two reduction chunks, two channel blocks; (1,16,32,128,64):
-    eight chunks; (1,4,4,32,64): one tile. F(4x4) in fp32: <= 2.5e-5 max-norm measured at the benchmark sizes, 8e-5 asserted
+    eight chunks; (1,4,4,32,64): one tile; the last four: the reduction / written channel counts of the mode-3 entries of the tuned
+    file (up to 32 reduction chunks, up to four channel blocks), with the epilogue the inference fold runs (bias + residual add +
+    ReLU in one call) in both inference forms. F(4x4) in fp32: <= 2.5e-5 max-norm measured at the benchmark sizes, 8e-5 asserted
     like the other F(4x4) passes (tests/test_conv_fullsize_gpu.py)."""
     import torch.nn.functional as Fn
     from denet_amd import ops
@@ -290,12 +295,22 @@ def test_fused_winograd_f4_tile_parallel_kernel(hip, case):
         for _ in range(2):
             y4 = ops.conv_fwd(x, w, bias=bias, stride=1, pad=1, relu=True, cache=icache)
             assert torch.equal(y4, y3) and icache["fwd_tile"] == ops.FUSED4
+        # the epilogue of a folded residual block's last convolution (layer/resnet.py: forward_folded(add=res, relu=True)):
+        # bias + residual add + ReLU in one call
+        r6 = r2.clamp_min(0)
+        y6 = ops.conv_fwd(x, w, bias=bias, add=addt, stride=1, pad=1, relu=True, cache=icache)
+        assert icache["fwd_tile"] == ops.FUSED4
+        assert float((y6.double() - r6).abs().max()) / float(r6.abs().max()) <= BOUND
+        assert bool((y6 >= 0).all()) and bool((y6 == 0).any())
         # ... and a mode-3 entry of the tuned file overrides the training decision for the inference forward pass only
         ops._WINO[(0, g)] = 0
         ops._WINO[(3, g)] = ops.FUSED4
         icache = {}
         y5 = ops.conv_fwd(x, w, bias=bias, stride=1, pad=1, relu=True, cache=icache)
         assert torch.equal(y5, y3) and icache["fwd_tile"] == ops.FUSED4
+        y7 = ops.conv_fwd(x, w, bias=bias, add=addt, stride=1, pad=1, relu=True, cache=icache)
+        assert icache["fwd_tile"] == ops.FUSED4 and torch.equal(y7, y6)
+        assert float((y7.double() - r6).abs().max()) / float(r6.abs().max()) <= BOUND
         tcache = {"train": True}
         ops.conv_fwd(x, w, bias=bias, stride=1, pad=1, relu=True, cache=tcache)
         assert tcache["fwd_tile"] == 0
