@@ -12,7 +12,10 @@ Inputs are resident in HBM before the timed region. Rank 0 prints ONE JSON line.
 process group reports it, per-rank ms/step, all-reduce bytes and buckets per step, event-timed exposed collective time).
 `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs), for comparing two builds.
 
-Extra legs (rank 0, N=1 only; outside the timed region):
+A plain run stops there: set-up, warm-up, the timed steps, the dump, the line. `--full` adds, outside the timed region, the
+per-layer kernel audit (config.kernels_used, every rank) and the extra legs below; `--no-<leg>` leaves one of them out.
+
+Extra legs (--full; rank 0, N=1 only; outside the timed region):
   roofline      the dominant kernel (the matrix-kernel SYMBOL with the largest total time, named as rocprofv3 names it) is timed
                 live with HIP events on the launch stream over `steps` further instrumented steps;
                 achieved = algorithmic FLOPs per launch / average launch duration; peak = fp32 MFMA 157.3 TFLOP/s.
@@ -429,6 +432,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run the kernel audit and every extra leg (roofline, in-step timing, input_h2d, "
+                         "warm / stress regimes, RCCL self-test, config2 / config5, split_bf16, inference, CPU baseline); "
+                         "the --no-* options below leave single ones out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-warm", action="store_true", help="skip the warm / stress corner-regime legs (rank 0, N=1)")
@@ -453,6 +460,9 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    if not args.full:           # a plain run: the headline alone, no audit step and no extra leg behind the timed steps
+        for leg in ("cpu_baseline", "roofline", "warm", "dp_selftest", "configs", "instep", "h2d", "audit", "inference", "split_bf16"):
+            setattr(args, "no_" + leg, True)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)          # does not return
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-F="--steps 10 --warmup 3 --no-cpu-baseline --no-warm --no-split-bf16 --no-configs --no-dp-selftest --no-h2d --no-instep --no-audit"
+F="--full --steps 10 --warmup 3 --no-cpu-baseline --no-warm --no-split-bf16 --no-configs --no-dp-selftest --no-h2d --no-instep --no-audit"
 for v in 1 0; do
   DENET_BN_FINAL_FOLD=$v python bench.py $F 2>/dev/null | python -c "
 import sys,json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A / B of two tuned files on the inference leg (get_detections, B = 32, hard NMS): bash tools/exp/ab_infer.sh <fileA> <fileB> [pairs]
 A="$1"; B="$2"; N=${3:-3}
-CMD="python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-warm --no-split-bf16 --no-configs --no-dp-selftest --no-h2d --no-instep --no-audit --no-roofline"
+CMD="python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-warm --no-split-bf16 --no-configs --no-dp-selftest --no-h2d --no-instep --no-audit --no-roofline"
 val() { python -c "
 import json,sys
 for l in sys.stdin:
