@@ -145,6 +145,10 @@ class BatchNormLayer(AbstractLayer):
             out_act.bn_producer = self
             return
         else:
+            probe = getattr(ctx, "bn_probe", None)
+            if probe is not None and probe[0] is self:
+                # model/update_bn.py: the moments of the raw input of this layer, taken before it normalises
+                ops.bn_moments_accumulate(x, probe[1], probe[2])
             y = ops.bn_fwd_test(x, self.omega.dev, self.beta.dev, self.mean.dev, self.stdinv.dev, self.eps, relu=relu,
                                 res=res, cache=self.__dict__.setdefault("_infer_cache", {}))
         out_act.data = y

@@ -108,6 +108,9 @@ SIGNATURES = {
     "denet_bn_bwd_final": (I, [P, I, L, I, P, P, P, P]),
     "denet_conv_wino_wgrad_dm": (I, [P, P, P, P, P, Z, P, Z] + [I] * 6 + [P]),
     "denet_bn_fwd_test": (I, [P] * 8 + [I, L, I, F, I, P]),
+    "denet_bn_moments_workspace_bytes": (Z, [L, I]),
+    "denet_bn_moments_accumulate": (I, [P, P, P, Z, L, I, P]),
+    "denet_bn_moments_finish": (I, [P, L, F, P, P, I, P]),
     "denet_bn_bwd": (I, [P] * 12 + [L, I, I, P]),
     "denet_maxpool_fwd": (I, [P, P, P] + [I] * 9 + [P]),
     "denet_maxpool_bwd": (I, [P, P, P] + [I] * 9 + [P]),

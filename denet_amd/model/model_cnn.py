@@ -104,6 +104,7 @@ class StepContext:
     def __init__(self, model):
         self.model = model
         self.has_sparse = any(l.type_name == "denet-sparse" for l in model.layers)
+        self.bn_probe = None       # (batch norm layer, acc, workspace): test mode accumulates the moments of its input (update_bn.py)
 
 
 class ModelCNN:
@@ -374,9 +375,11 @@ class ModelCNN:
                         counts[id(a)] = counts.get(id(a), 0) + 1
         return counts.get(id(act), 0)
 
-    def forward(self, data_x, data_m=None, train=True):
+    def forward(self, data_x, data_m=None, train=True, stop_after=None, bn_probe=None):
         """runs the layers in order; in training mode get_target of layer i is called right before its forward
-        (so DNS sees the corner map of this very pass and DND sees the edited RoI list)"""
+        (so DNS sees the corner map of this very pass and DND sees the edited RoI list).
+        stop_after: a top-level layer after which the pass ends (None: all layers). bn_probe: (batch norm layer, acc, workspace),
+        the layer adds the moments of its input to acc in test mode (model/update_bn.py)"""
         layer_mod.set_train(train)
         if not self._packed:
             self.pack_device()
@@ -390,6 +393,7 @@ class ModelCNN:
             step_begin.record()
         self._upload_input(data_x)
         ctx = StepContext(self)
+        ctx.bn_probe = bn_probe
         fold = (not train) and ops.INFER_FOLD
         skip_next = False
         for i, layer in enumerate(self.layers[1:]):
@@ -406,6 +410,8 @@ class ModelCNN:
                     layer.forward_folded(ctx, nxt, relu=nxt.type_name == "batchnorm-relu" or act is not None,
                                          out_act=act.output if act is not None else None)
                     skip_next = True
+                    if stop_after is layer or stop_after is nxt:
+                        break
                     continue
             if train and data_m is not None:
                 layer.prepare_target(ctx, self, data_x, data_m)
@@ -424,6 +430,8 @@ class ModelCNN:
                 # device is not left idle in front of it
                 for other in self.layers[2:]:
                     other.begin_step(data_m)
+            if layer is stop_after:
+                break
         return ctx
 
     def backward(self, ctx):

@@ -3,6 +3,7 @@
 Tensors are NHWC fp32, contiguous, on the current HIP device. No torch arithmetic happens here; every
 function enqueues hand-written HIP kernels on the current torch stream and returns.
 """
+import contextlib
 import os
 
 import torch
@@ -1485,6 +1486,41 @@ def bump_weights_version():
 
 
 INFER_FOLD = os.environ.get("DENET_INFER_FOLD", "1") != "0"      # inference: batch norm folded into the convolution in front
+
+
+@contextlib.contextmanager
+def infer_fold(enabled):
+    """INFER_FOLD set to `enabled` inside the block, restored on the way out (model/update_bn.py: a batch norm folded into the
+    convolution in front never runs its own forward, and its input holds normalised values)"""
+    global INFER_FOLD
+    was = INFER_FOLD
+    INFER_FOLD = bool(enabled)
+    try:
+        yield
+    finally:
+        INFER_FOLD = was
+
+
+def bn_moments_workspace(M, C):
+    return WS.get("bn_moments", _L().denet_bn_moments_workspace_bytes(M, C))
+
+
+def bn_moments_accumulate(x, acc, ws=None):
+    """acc (float64 [2][C] on the device) += per-channel mean and biased variance of x [.., C] (update_bn.py:55-60)"""
+    C = x.shape[-1]
+    M = x.numel() // C
+    ws = bn_moments_workspace(M, C) if ws is None else ws
+    check(_L().denet_bn_moments_accumulate(ptr(x), ptr(acc), ptr(ws), ws.numel() * ws.element_size(), M, C, stream_ptr()),
+          "bn_moments_accumulate")
+
+
+def bn_moments_finish(acc, n, mean_dev, stdinv_dev, eps=1e-5):
+    """running statistics from n accumulated batches, written on the device (update_bn.py:62-66); the inference caches derived
+    from them (test coefficients, folded filters) are invalidated"""
+    C = acc.shape[-1]
+    check(_L().denet_bn_moments_finish(ptr(acc), int(n), float(eps), ptr(mean_dev), ptr(stdinv_dev), C, stream_ptr()),
+          "bn_moments_finish")
+    bump_weights_version()
 
 
 def bn_fold(w, conv_bias, gamma, beta, run_mean, run_stdinv, eps):

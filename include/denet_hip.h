@@ -374,6 +374,17 @@ int denet_bn_bwd_apply(const float* x, const float* y, const float* dy, const fl
 int denet_bn_fwd_test(const float* x, const float* res, float* y, const float* gamma, const float* beta,
                       const float* run_mean, const float* run_stdinv, float* coef, int coef_ready, long M, int C, float eps,
                       int relu, hipStream_t stream);
+/* re-estimation of a batch norm's running statistics (model-update-bn, denet/model/update_bn.py:52-70; csrc/bn_moments.hip).
+ *   accumulate: x [M][C] (C % 4 == 0) -> acc[0][c] += mean_c, acc[1][c] += biased variance_c of this batch; acc = [2][C] doubles
+ *               owned by the caller (zeroed before the first batch). Partial sums of the values shifted by the first row, fp64,
+ *               one slab row per workgroup, folded by a second launch: no atomics, bitwise reproducible. workspace: at least
+ *               denet_bn_moments_workspace_bytes(M, C) bytes.
+ *   finish:     run_mean = f32(acc[0] / n), run_stdinv = 1 / sqrt(f32(acc[1] / n) + eps) evaluated in float32 with correctly
+ *               rounded operations (update_bn.py:63-66 uses eps = 1e-5, not the layer's). */
+size_t denet_bn_moments_workspace_bytes(long M, int C);
+int denet_bn_moments_accumulate(const float* x, double* acc, void* workspace, size_t workspace_bytes, long M, int C,
+                                hipStream_t stream);
+int denet_bn_moments_finish(const double* acc, long n, float eps, float* run_mean, float* run_stdinv, int C, hipStream_t stream);
 /* inference: conv(x, w) + b followed by test-mode batch norm == conv(x, w_out) + b_out (batch_norm.py:50-52 incl. its
  * double epsilon). w: [K][per_k] KRSC filters, conv_bias: [K] or NULL. */
 int denet_bn_fold(const float* w, const float* conv_bias, const float* gamma, const float* beta, const float* run_mean,
