@@ -11,7 +11,9 @@ from .. import ops
 
 
 def conv_padding(border_mode, k):
-    """symmetric zero padding implied by a Theano border mode for a k-wide filter"""
+    """symmetric zero padding implied by a Theano border mode for a k-wide filter. `same` with an even k is the padding k // 2
+    with the output cut to the input's size (same_crop): the reference takes the full convolution and crops it at (k - 1) // 2
+    (convolution.py:66-69,76-80), i.e. pads k // 2 rows / columns in front and (k - 1) // 2 behind"""
     if border_mode == "valid":
         return 0
     if border_mode == "full":
@@ -19,15 +21,18 @@ def conv_padding(border_mode, k):
     if border_mode == "half":
         return k // 2
     if border_mode == "same":
-        if k % 2 == 0:
-            raise NotImplementedError("border_mode 'same' with an even filter needs asymmetric padding")
-        return (k - 1) // 2
+        return k // 2
     if isinstance(border_mode, (tuple, list)):
         assert border_mode[0] == border_mode[1], "only symmetric padding is supported"
         return int(border_mode[0])
     if isinstance(border_mode, int):  # includes False == 0 (denet_corner.py:39)
         return int(border_mode)
     raise Exception("Unknown border mode: " + str(border_mode))
+
+
+def same_crop(border_mode, k):
+    """True when the output of conv_padding's symmetric padding loses its last row and column (`same`, even k)"""
+    return border_mode == "same" and k % 2 == 0
 
 
 class ConvLayer(AbstractLayer):
@@ -90,6 +95,11 @@ class ConvLayer(AbstractLayer):
         # output shape (convolution.py:55-74)
         oh = int(math.ceil((self.input_shape[-2] + 2 * self.pad - fs[2] + 1) / self.stride[0]))
         ow = int(math.ceil((self.input_shape[-1] + 2 * self.pad - fs[3] + 1) / self.stride[1]))
+        # `same` with an even filter: the passes get the output size explicitly (ops.conv_geom's ohw), None = the derived one
+        self.ohw = None
+        if same_crop(self.border_mode, fs[2]):
+            oh, ow = self.input_shape[-2], self.input_shape[-1]
+            self.ohw = (oh, ow)
         self.output_shape = (self.input_shape[0], fs[0], oh, ow)
         self.output = Act(self.output_shape, self.kp, "conv%i" % self.layer_index)
 
@@ -163,8 +173,8 @@ class ConvLayer(AbstractLayer):
             # the network input, still in the reference's planar layout: the first layer's kernels read it as it is (forward and,
             # in backward(), the filter gradient); anybody else who asks the Act for .data gets the NHWC tensor made then
             self.input.set_pending_data(link)
-            if add is None and self.use_bias and ops.conv_stem_ok(link.x, self.omega.dev_shape, self.stride[0], self.pad,
-                                                                   self.filter_shape[3]):
+            if add is None and self.use_bias and self.ohw is None and ops.conv_stem_ok(link.x, self.omega.dev_shape, self.stride[0],
+                                                                                        self.pad, self.filter_shape[3]):
                 self.output.data = ops.conv_stem_fwd(link.x, self._w(), self.beta.dev, cache, want_stats, logical=self._logical())
                 self.output.stats = cache.pop("bn_stats", None) if want_stats else None
                 self._planar_x = link.x
@@ -183,7 +193,7 @@ class ConvLayer(AbstractLayer):
             cache["bn_final"] = sbn.stats_final(skip.output) if sbn is not None else None
             y = ops.conv_fwd(x, self._w(), bias=None, add=skip.y.data, stride=self.stride[0], pad=self.pad,
                              s_real=self.filter_shape[3], logical=self._logical(), cache=cache, bn_stats=want_skip_stats, link=link,
-                             up=up)
+                             up=up, ohw=self.ohw)
             if link is not None:
                 self.input.data = link.materialise()
             self._settle_up(up)
@@ -197,7 +207,7 @@ class ConvLayer(AbstractLayer):
         cache["bn_final"] = sbn.stats_final(self.output) if sbn is not None else None
         self.output.data = ops.conv_fwd(x, self._w(), bias=self.beta.dev if self.use_bias else None, add=add,
                                         stride=self.stride[0], pad=self.pad, s_real=self.filter_shape[3],
-                                        logical=self._logical(), cache=cache, bn_stats=want_stats, link=link, up=up)
+                                        logical=self._logical(), cache=cache, bn_stats=want_stats, link=link, up=up, ohw=self.ohw)
         if link is not None:
             self.input.data = link.materialise()
         self._settle_up(up)
@@ -226,7 +236,8 @@ class ConvLayer(AbstractLayer):
         link = self.input.take_pending_data()
         if isinstance(link, ops.NchwLink):
             self.input.set_pending_data(link)          # (see forward: the first layer reads the planar batch)
-            if add is None and ops.conv_stem_ok(link.x, self.omega.dev_shape, self.stride[0], self.pad, self.filter_shape[3]):
+            if add is None and self.ohw is None and ops.conv_stem_ok(link.x, self.omega.dev_shape, self.stride[0], self.pad,
+                                                                     self.filter_shape[3]):
                 y = ops.conv_stem_fwd(link.x, ent[2], ent[3], cache, False, logical=self._logical(), relu=relu)
                 self.output.data = y
                 (out_act if out_act is not None else bn.output).data = y
@@ -234,7 +245,7 @@ class ConvLayer(AbstractLayer):
         elif link is not None:
             self.input.data = link.materialise()
         y = ops.conv_fwd(self.input.data, ent[2], bias=ent[3], add=add, stride=self.stride[0], pad=self.pad,
-                         s_real=self.filter_shape[3], logical=self._logical(), cache=cache, relu=relu)
+                         s_real=self.filter_shape[3], logical=self._logical(), cache=cache, relu=relu, ohw=self.ohw)
         self.output.data = y
         (out_act if out_act is not None else bn.output).data = y
         return y
@@ -263,7 +274,7 @@ class ConvLayer(AbstractLayer):
             # data- and filter-gradient passes are Winograd passes forms it inside ONE transform kernel that feeds both
             fs = self.filter_shape
             if (self.enabled and self.omega.grad is not None and getattr(self.input, "requires_grad", True) and not self.use_bias
-                    and fs[2] == 3 and fs[3] == 3 and st == 1 and self.stride[1] == 1 and pad == 1):
+                    and fs[2] == 3 and fs[3] == 3 and st == 1 and self.stride[1] == 1 and pad == 1 and self.ohw is None):
                 dx = ops.conv_backward_linked(link, x, self._w(), self.omega.dev_shape, self.input.grad,
                                               self.omega.grad.view(self.omega.dev_shape), self._cache(), stride=st, pad=pad,
                                               s_real=sr, logical=self._logical(), sums=sums)
@@ -280,7 +291,7 @@ class ConvLayer(AbstractLayer):
         first = need_dx and sr == 1 and st == 1 and 2e-9 * dy.numel() * x_shape[-1] >= ops.DGRAD_FIRST_GFLOP
         if first:
             self.input.grad = ops.conv_dgrad(dy, self._w(), x_shape, add=self.input.grad, stride=st, pad=pad,
-                                             s_real=sr, logical=self._logical(), cache=self._cache(), sums=sums)
+                                             s_real=sr, logical=self._logical(), cache=self._cache(), sums=sums, ohw=self.ohw)
             self.input.grad_sums = sums
         if self.enabled and self.omega.grad is not None:
             # the first layer of the network has no data gradient: its filter gradient is the tail of the backward sweep on the
@@ -296,12 +307,12 @@ class ConvLayer(AbstractLayer):
                         x = self.input.data          # (written here, on the filter-gradient stream)
                     ops.conv_wgrad(x, dy, self.omega.dev_shape, stride=st, pad=pad, s_real=sr,
                                    out=self.omega.grad.view(self.omega.dev_shape), logical=self._logical(),
-                                   cache=self._cache())
+                                   cache=self._cache(), ohw=self.ohw)
                 if self.use_bias and not tail:
                     ops.colsum(dy.view(-1, self.kp), out=self.beta.grad)
             if self.use_bias and tail:
                 ops.colsum(dy.view(-1, self.kp), out=self.beta.grad)
         if need_dx and not first:
             self.input.grad = ops.conv_dgrad(dy, self._w(), x_shape, add=self.input.grad, stride=st, pad=pad,
-                                             s_real=sr, logical=self._logical(), cache=self._cache(), sums=sums)
+                                             s_real=sr, logical=self._logical(), cache=self._cache(), sums=sums, ohw=self.ohw)
             self.input.grad_sums = sums

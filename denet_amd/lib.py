@@ -111,6 +111,9 @@ SIGNATURES = {
     "denet_bn_moments_workspace_bytes": (Z, [L, I]),
     "denet_bn_moments_accumulate": (I, [P, P, P, Z, L, I, P]),
     "denet_bn_moments_finish": (I, [P, L, F, P, P, I, P]),
+    "denet_regression_workspace_bytes": (Z, [I, I]),
+    "denet_regression_loss": (I, [P] * 6 + [Z] + [I] * 5 + [P]),
+    "denet_regression_probs": (I, [P] * 3 + [I] * 5 + [P]),
     "denet_bn_bwd": (I, [P] * 12 + [L, I, I, P]),
     "denet_maxpool_fwd": (I, [P, P, P] + [I] * 9 + [P]),
     "denet_maxpool_bwd": (I, [P, P, P] + [I] * 9 + [P]),

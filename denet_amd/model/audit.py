@@ -30,7 +30,7 @@ def conv_layers(model):
 def layer_geometry(layer):
     """(fwd geometry tuple of ops.conv_geom, human-readable string) of a ConvLayer on its physical NHWC tensors"""
     n, _, h, w = layer.input_shape
-    g = ops.conv_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride[0], layer.pad, layer.filter_shape[3])
+    g = ops.conv_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride[0], layer.pad, layer.filter_shape[3], layer.ohw)
     fs = layer.filter_shape
     return g, "%dx%d %d->%d %dx%d/%d" % (h, w, fs[1], fs[0], fs[2], fs[3], layer.stride[0])
 

@@ -614,6 +614,8 @@ class ModelCNN:
         self.forward(data_x, None, train=False)
         last = self.layers[-1]
         out = last.output.data
+        if last.type_name == "regression" and last.views is not None:
+            return last.probabilities(out).cpu().numpy()       # a spatial map: the mean over the views, on the device
         if last.type_name == "regression":
             # regression.py:44-50: output = exp(log_softmax(x)); B x C values, evaluated on the host
             B, C = last.output_shape

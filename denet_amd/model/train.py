@@ -1,9 +1,9 @@
 """model-train — single-GPU training driver with the CLI flag surface of the reference's denet/model/train.py
 (:46-156): --model / --model-desc, --solver, --learn-rate, --learn-momentum, --learn-decay, --learn-anneal,
 --learn-anneal-epochs, --batch-size, --seed, --border-mode, --activation, --weight-init, --cost-factors, --epochs,
---output-prefix. The reference's dataset loaders are outside the hot path; `--train synthetic[,k=v]`
-feeds MSCOCO-shaped synthetic batches with the same meta-dict contract (image_loader.py:134-136), and any object
-with `export(batch_size) -> (x, metas, n)` (dataset/__init__.py:349-366) can be passed to train() directly."""
+--output-prefix, --skip-train; --distort-mode and --test-mode are parsed and unused, as in the reference (:58, :73).
+The reference's dataset loaders are outside the hot path; `--train synthetic[,k=v]` feeds
+MSCOCO-shaped synthetic batches with the same meta-dict contract (image_loader.py:134-136), and any object with `export(batch_size) -> (x, metas, n)` (dataset/__init__.py:349-366) can be passed to train() directly."""
 import argparse
 import math
 import random
@@ -82,7 +82,8 @@ def load_dataset(spec, seed, extension="ppm", is_training=True, thread_num=1, cl
     return SyntheticDataset(seed=seed, **kw)
 
 
-def build_parser():
+def build_parser(single=True):
+    """the flags of train.py:46-78; single=False leaves out those model-train-multi does not share (--test-mode, --skip-train)"""
     parser = argparse.ArgumentParser(description="Train a convolutional network (MI355X hot path of lachlants/denet)")
     from ..common import logging
     logging.add_arguments(parser)
@@ -92,6 +93,8 @@ def build_parser():
                         help="training data folder, or synthetic[,samples=N,image=S,classes=C]")
     parser.add_argument("--test", default=None, help="The folder with testing data (optional)")
     parser.add_argument("--test-epochs", type=int, default=1, help="Epochs between each test evaluation")
+    if single:
+        parser.add_argument("--test-mode", default="default", help="Mode to use for testing (parsed, unused: train.py:58)")
     parser.add_argument("--extension", default="ppm", help="Image file extension / dataset format string")
     parser.add_argument("--thread-num", type=int, default=1, help="Worker processes for loading / augmenting data")
     parser.add_argument("--max-samples", type=int, default=None, help="Maximum samples to load from training set")
@@ -112,7 +115,12 @@ def build_parser():
     parser.add_argument("--epochs", type=int, default=30)
     parser.add_argument("--batch-size", type=int, default=32)
     parser.add_argument("--seed", type=int, default=23455)
+    parser.add_argument("--distort-mode", default=[], nargs="+",
+                        help="Distortions to apply to training data (parsed, unused: the reference never reads it, train.py:73)")
     parser.add_argument("--disable-intermediate", default=False, action="store_true")
+    if single:
+        parser.add_argument("--skip-train", default=False, action="store_true",
+                            help="Skip training of model (epochs still anneal, test and save)")
     parser.add_argument("--skip-layer-updates", type=int, nargs="+", default=[])
     parser.add_argument("--model-desc", default=["C[100,7]", "P[2]", "C[150,4]", "P[2]", "C[250,4]", "P[2]", "C[300,1]", "R"],
                         nargs="+", type=str)
@@ -152,7 +160,9 @@ def train(args, train_data, log=None, test_data=None):
     """the epoch loop of train.py:117-151 (shuffle, train_epoch, learning-rate annealing, checkpoint per epoch)"""
     log = _default_log() if log is None else log
     model = model_cnn.initialize(args, train_data.get_data_shape(), train_data.class_labels, train_data.get_class_num())
-    model.build_train_func(args.solver, args.cost_factors)
+    skip_train = getattr(args, "skip_train", False)
+    if not skip_train:
+        model.build_train_func(args.solver, args.cost_factors)
     learn_rate = args.learn_rate
     costs = []
     device_loader = None
@@ -161,8 +171,9 @@ def train(args, train_data, log=None, test_data=None):
         device_loader = DeviceImageLoader(max(1, getattr(args, "thread_num", 1)), True, cp=model.input.cp, decode="process",
                                           params=train_data.image_loader)
     for epoch in range(args.epochs):
-        train_data.shuffle()
-        for subset in range(train_data.subset_num):
+        if not skip_train:
+            train_data.shuffle()
+        for subset in range(0 if skip_train else train_data.subset_num):
             if device_loader is not None:
                 lo = subset * train_data.subset_size
                 hi = min((subset + 1) * train_data.subset_size, train_data.subset_total_size)

@@ -146,9 +146,8 @@ def find_restart(output_prefix):
     return files[-1], int(v[-2][5:]), int(v[-1][6:]) + 1
 
 
-def main(argv=None):
-    import torch
-    parser = train_mod.build_parser()
+def build_parser():
+    parser = train_mod.build_parser(single=False)
     parser.add_argument("--batch-size-factor", type=int, default=1,
                         help="local training steps per rank between two parameter averagings (1: gradient all-reduce every step)")
     parser.add_argument("--use-acc-mode", default=False, action="store_true",
@@ -158,7 +157,12 @@ def main(argv=None):
     parser.add_argument("--subset-start", type=int, default=0, help="Subset to start from")
     parser.add_argument("--restart", default=False, action="store_true", help="Restart training of model")
     parser.add_argument("--save-subsets", default=False, action="store_true", help="checkpoint after every subset")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    import torch
+    args = build_parser().parse_args(argv)
     if args.restart:
         args.model, args.epoch_start, args.subset_start = find_restart(args.output_prefix)
     from ..common import logging

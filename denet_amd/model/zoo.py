@@ -5,6 +5,7 @@
                   --convert-bn-relu --class-num --image-size 512 512 --layer-remove 3
                   --layer-insert 11:SKIPSRC.X[0] 18:SKIPSRC.X[1] -> --layer-append <skip desc>   (config 3/4)
   cifar3          README.md:52 three-layer CNN (config 1; `P.A` needs an explicit size in this code version)
+  simple_cifar10  examples/simple-cifar10.sh: nine-layer CNN with 2x2 `same` layers, dropout and a centre-pixel `R.C[6]` head
 plus the synthetic MSCOCO-shaped batches of SURVEY.md §8(d).
 """
 import numpy
@@ -26,6 +27,8 @@ DENET101_WIDE_DESC = ("PI[2] C[1024,3] SKIP[2] BNA PI[2] C[512,3] SKIP[1] BNA PI
 DENET101_SKIP_DESC = ("PI[2] C.B[384,3] SKIP[1] BNA PI[2] C.B[192,3] SKIP[0] BNA DNC[128,50] DNS[7,24,0.01,0.1] C.B[2048,1] BNA "
                       "C.B[1536,1] BNA C.B[1024,1] BNA C.B[768,1] BNA DND[0.5,1,1]")
 CIFAR3_DESC = "C[128,3] BN A P[2] C[256,3] BN A P[2] C[512,3] BN A P.A[8] R"
+SIMPLE_CIFAR10_DESC = ("B[3] C[128,3] BN A C[96,2] BN A C[64,1] BN A P.A[2] D[0.2] C[256,3] BN A C[192,2] BN A C[128,1] BN A "
+                       "P.A[2] D[0.2] C[512,3] BN A C[384,2] BN A C[256,1] BN A D[0.2] R.C[6]")
 
 
 def resnet34(batch_size, image=224, class_num=1000, seed=1):
@@ -92,6 +95,16 @@ def cifar3(batch_size=32, class_num=10, seed=1):
     m.batch_size = batch_size
     m.class_num = class_num
     m.build(CIFAR3_DESC, (3, 32, 32), "relu", "half", ["he-backward"])
+    return m
+
+
+def simple_cifar10(batch_size=32, class_num=10, seed=1):
+    """the getting-started recipe (--border-mode same): 38x38 after the border, 4x4 logits, cost at the centre pixel"""
+    numpy.random.seed(seed)
+    m = model_cnn.ModelCNN()
+    m.batch_size = batch_size
+    m.class_num = class_num
+    m.build(SIMPLE_CIFAR10_DESC, (3, 32, 32), "relu", "same", ["he-backward"])
     return m
 
 

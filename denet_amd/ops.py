@@ -260,14 +260,25 @@ def _conv_flops(g, logical=None):
     return 2.0 * N * OH * OW * K * R * s_real * C
 
 
-def conv_geom(x_shape, w_shape, stride, pad, s_real=None):
+def conv_geom(x_shape, w_shape, stride, pad, s_real=None, ohw=None):
+    """the geometry tuple of the C ABI. ohw = (OH, OW): an output cut short of the one the symmetric padding gives (the last rows /
+    columns dropped): `same` with an even filter is the padding k // 2 with the output cut to H x W (ConvLayer)"""
     N, H, W, C = x_shape
     K, R, S, Cw = w_shape
     assert Cw == C, (x_shape, w_shape)
     s_real = S if s_real is None else s_real
     OH = (H + 2 * pad - R) // stride + 1
     OW = (W + 2 * pad - s_real) // stride + 1
+    if ohw is not None:
+        assert 0 < ohw[0] <= OH and 0 < ohw[1] <= OW, (ohw, OH, OW)
+        OH, OW = int(ohw[0]), int(ohw[1])
     return N, H, W, C, K, R, S, s_real, stride, pad, OH, OW
+
+
+def _full(g):
+    """the output is the whole one of the symmetric padding: only the direct kernels take a cut one (conv_geom's ohw)"""
+    N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
+    return OH == (H + 2 * pad - R) // stride + 1 and OW == (W + 2 * pad - s_real) // stride + 1
 
 
 # DENET_AUTOTUNE=0 ignores the committed decisions and the Winograd / fused algorithms: built-in launch heuristics, direct kernels
@@ -548,7 +559,7 @@ def _wgrad_dm(x, dm, v, dw, tile, N, H, W, C, K):
 def _bf16x3_geom(g):
     N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
     return HEAD_BF16X3 and R == 1 and S == 1 and stride == 1 and pad == 0 and C >= 512 and C % 128 == 0 and K % 128 == 0 \
-        and (N * H * W) % 32 == 0
+        and (N * H * W) % 32 == 0 and _full(g)
 
 
 def _gemm_bf16x3(a, b, bias, out, M, N, K):
@@ -563,13 +574,13 @@ def _transpose(src, R, C, out=None):
 
 
 def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, logical=None, cache=None, relu=False,
-             bn_stats=False, link=None, up=None):
+             bn_stats=False, link=None, up=None, ohw=None):
     """bn_stats (training, the layer behind is a batch norm): the epilogue of the pass also writes the per-channel sums of y;
     cache["bn_stats"] = (partial sums tensor, rows) for bn_fwd_train(pre=...), or None when the chosen kernel cannot.
     link (BnLink, x = None): the input is the output of a batch norm whose pointwise pass has not run; a Winograd pass evaluates
     it inside its input transform, every other implementation materialises it first. link.result is the activation afterwards."""
     if link is not None:
-        g = conv_geom(link.x.shape, w.shape, stride, pad, s_real)
+        g = conv_geom(link.x.shape, w.shape, stride, pad, s_real, ohw)
         tile = _decided(0, g)
         if not (tile in (2, 4) and cache is not None and cache.get("train") and not relu and not _bf16x3_geom(g)):
             x = link.materialise()             # direct / fused-64 / undecided implementations read the tensor itself
@@ -582,12 +593,12 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
         # up (UpLink, x = None): the input is a pool-inverse layer's output that has not been written. A training pass on the
         # un-fused Winograd kernels (already decided for this geometry) reads the small tensor in its input transform; every other
         # case writes the up-sampled tensor first
-        gu = conv_geom(up.shape, w.shape, stride, pad, s_real)
+        gu = conv_geom(up.shape, w.shape, stride, pad, s_real, ohw)
         if not (_decided(0, gu) in (2, 4) and ((0, gu) in _TUNED or not AUTOTUNE or not MEASURE or POLICY is not None) and cache is not None and cache.get("train") and bn_stats
                 and not relu and not _bf16x3_geom(gu)):
             x = up.materialise()
             up = None
-    g = conv_geom(up.shape if up is not None else x.shape, w.shape, stride, pad, s_real)
+    g = conv_geom(up.shape if up is not None else x.shape, w.shape, stride, pad, s_real, ohw)
     N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
     y = out if out is not None else empty(N, OH, OW, K)
     if add is None and not relu and _bf16x3_geom(g):
@@ -728,7 +739,7 @@ def _filter_tile(tile):
 def conv_wino4t_ok(mode, g):
     """geometry the tile-parallel fused F(4x4,3x3) kernel covers for the forward pass (mode 0) / the data gradient (1)"""
     N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
-    if not (mode in (0, 1) and R == 3 and S == 3 and s_real == 3 and stride == 1 and pad == 1):
+    if not (mode in (0, 1) and R == 3 and S == 3 and s_real == 3 and stride == 1 and pad == 1 and _full(g)):
         return False
     red, out = (C, K) if mode == 0 else (K, C)
     return bool(_L().denet_conv_wino4t_ok(N, H, W, red, out))
@@ -738,7 +749,7 @@ def conv_wino2f_ok(mode, g):
     """geometry the fused F(2x2,3x3) kernels cover for the forward pass (mode 0) / the data gradient (1) / the filter
     gradient (2)"""
     N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
-    if not (R == 3 and S == 3 and s_real == 3 and stride == 1 and pad == 1):
+    if not (R == 3 and S == 3 and s_real == 3 and stride == 1 and pad == 1 and _full(g)):
         return False
     if mode == 2:
         return bool(_L().denet_conv_wino2f_wgrad_ok(N, H, W, C, K))
@@ -765,7 +776,7 @@ def conv_wino_ok(g, tile=2):
     7x7 maps of ResNet-34 at 224x224 run F(4x4) on 16x16 / 8x8 tile grids); DENET_WINO_RAGGED=0 restores the multiples-only rule"""
     N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
     return R == 3 and S == 3 and s_real == 3 and stride == 1 and pad == 1 and (WINO_RAGGED or (H % tile == 0 and W % tile == 0)) \
-        and H >= tile and W >= tile and C % 32 == 0 and K % 32 == 0
+        and H >= tile and W >= tile and C % 32 == 0 and K % 32 == 0 and _full(g)
 
 
 def _wino_tile(mode, g, direct, wino):
@@ -1106,8 +1117,8 @@ def conv_wino4t_filter(w, dgrad, out=None):
     return pk
 
 
-def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None, logical=None, cache=None, sums=None):
-    g = conv_geom(x_shape, w.shape, stride, pad, s_real)
+def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None, logical=None, cache=None, sums=None, ohw=None):
+    g = conv_geom(x_shape, w.shape, stride, pad, s_real, ohw)
     assert tuple(dy.shape) == (g[0], g[10], g[11], g[4]), (dy.shape, g)
     dx = out if out is not None else empty(*x_shape)
     if add is None and _bf16x3_geom(g):
@@ -1116,7 +1127,7 @@ def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None,
             cache["dgrad_tile"] = 0
         return _gemm_bf16x3(dy, _transpose(w, K, C), None, dx, N * H * W, C, K)       # dx[pix][c] = dy[pix][k] (w^T)[c][k]^T
     if DGRAD_1X1T_GFLOP > 0 and g[5] == 1 and g[6] == 1 and g[8] == 1 and g[9] == 0 and g[3] % 32 == 0 and g[4] % 32 == 0 \
-            and 2e-9 * dy.numel() * g[3] >= DGRAD_1X1T_GFLOP:
+            and 2e-9 * dy.numel() * g[3] >= DGRAD_1X1T_GFLOP and _full(g):
         # a large 1x1 layer (the head): the forward kernel over the transposed filter (denet_conv_dgrad_1x1t, bit-identical);
         # the transposed copy comes from the side stream (wino_prefetch_filters) when a training step prepared it
         import ctypes
@@ -1142,7 +1153,7 @@ def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None,
         if sb is not None:
             sums.done(sb, rows.value, fin)
         return dx
-    if DGRAD_S2 and g[5] == 3 and g[6] == 3 and g[7] == 3 and g[8] == 2 and g[9] == 1 and \
+    if DGRAD_S2 and g[5] == 3 and g[6] == 3 and g[7] == 3 and g[8] == 2 and g[9] == 1 and _full(g) and \
             _L().denet_conv_dgrad_s2_ok(g[0], g[1], g[2], g[3], g[4]):
         # a 3x3 stride-2 layer (the first convolution of a ResNet stage): the four parity classes of input pixels in one
         # workgroup (csrc/dgrad_s2.hip); the packed filter comes from the side stream when a training step prepared it
@@ -1224,8 +1235,8 @@ def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None,
     return dx
 
 
-def conv_wgrad(x, dy, w_shape, stride=1, pad=0, s_real=None, out=None, logical=None, cache=None):
-    g = conv_geom(x.shape, w_shape, stride, pad, s_real)
+def conv_wgrad(x, dy, w_shape, stride=1, pad=0, s_real=None, out=None, logical=None, cache=None, ohw=None):
+    g = conv_geom(x.shape, w_shape, stride, pad, s_real, ohw)
     assert tuple(dy.shape) == (g[0], g[10], g[11], g[4]), (dy.shape, g)
     dw = out if out is not None else empty(*w_shape)
     if _bf16x3_geom(g):
@@ -1886,6 +1897,26 @@ def detect_loss(logits, det_target, bbox_valid, bbox_target, roi_bbox, dlogits, 
                                  ptr(fit_target), ptr(dlogits), ptr(costs), ptr(_loss_ws()), M, batch, CP, ncls, nreg,
                                  int(nfit), cost_factor, bbox_factor, float(fit_factor), int(bounded_iou), stream_ptr()),
           "detect_loss")
+
+
+def regression_loss(logits, offsets, cls, dlogits, costs, C):
+    """soft-max classification cost over the view pixels `offsets` (int32 [V], y * W + x) of the NHWC logit map [B, H, W, CP]
+    (regression.py:31-47,97-98): costs[0] = mean NLL of the class cls[b] (int32 [B]) over the B x V rows, costs[1] = 0;
+    dlogits (optional, the map's shape) = (softmax - onehot) / (B * V) at the views, zero elsewhere"""
+    B, H, W, CP = logits.shape
+    V = offsets.numel()
+    ws = WS.get("regression", _L().denet_regression_workspace_bytes(B, V))
+    check(_L().denet_regression_loss(ptr(logits), ptr(offsets), ptr(cls), ptr(dlogits), ptr(costs), ptr(ws), ws.numel(), B, H * W,
+                                     CP, C, V, stream_ptr()), "regression_loss")
+
+
+def regression_probs(logits, offsets, C, out=None):
+    """[B, C] mean over the views `offsets` of the soft-max of the logits there (regression.py:45-47)"""
+    B, H, W, CP = logits.shape
+    pr = out if out is not None else empty(B, C)
+    check(_L().denet_regression_probs(ptr(logits), ptr(offsets), ptr(pr), B, H * W, CP, C, offsets.numel(), stream_ptr()),
+          "regression_probs")
+    return pr
 
 
 def build_samples(corner_pr, corner_threshold, sample_count, max_corners=1024, local_max=0, out=None):

@@ -385,6 +385,20 @@ size_t denet_bn_moments_workspace_bytes(long M, int C);
 int denet_bn_moments_accumulate(const float* x, double* acc, void* workspace, size_t workspace_bytes, long M, int C,
                                 hipStream_t stream);
 int denet_bn_moments_finish(const double* acc, long n, float eps, float* run_mean, float* run_stdinv, int C, hipStream_t stream);
+/* soft-max classification over chosen pixels of a logit map (the `R` layer's view path, denet/layer/regression.py:23-47,97-98;
+ * csrc/regression.hip). logits: NHWC [B][HW][CP], C real classes; offsets: V DISTINCT pixel indices (y * W + x) in [0, HW); cls: [B]
+ * class per sample.
+ *   loss:  costs[0] = mean over the B * V (sample, view) rows of -log_softmax(logits[b, offsets[v]])[cls[b]], costs[1] = 0;
+ *          dlogits (optional) = the whole [B][HW][CP] map: (softmax - onehot) / (B * V) at the view pixels, 0 everywhere else
+ *          (padding channels included). One wave per row, any C; the rows' NLL go through a fixed-order sum in one workgroup
+ *          (no atomics, bitwise reproducible). workspace: at least denet_regression_workspace_bytes(B, V) bytes. The reference
+ *          indexes its (B, C, V) log-probabilities with b * C + cls, right only for V = 1 (:79-81); callers train with V = 1.
+ *   probs: pr [B][C] = mean over the views (summed in order v = 0 .. V-1) of the softmax of the view (:45-47). */
+size_t denet_regression_workspace_bytes(int B, int V);
+int denet_regression_loss(const float* logits, const int* offsets, const int* cls, float* dlogits, float* costs, void* workspace,
+                          size_t workspace_bytes, int B, int HW, int CP, int C, int V, hipStream_t stream);
+int denet_regression_probs(const float* logits, const int* offsets, float* pr, int B, int HW, int CP, int C, int V,
+                           hipStream_t stream);
 /* inference: conv(x, w) + b followed by test-mode batch norm == conv(x, w_out) + b_out (batch_norm.py:50-52 incl. its
  * double epsilon). w: [K][per_k] KRSC filters, conv_bias: [K] or NULL. */
 int denet_bn_fold(const float* w, const float* conv_bias, const float* gamma, const float* beta, const float* run_mean,
