@@ -1,9 +1,11 @@
 """`RSN` / `nRSN` — residual block. Mirrors denet/layer/resnet.py (ResnetLayer :13-167): original (post-activation)
 or pre-activation design, basic or bottleneck body, optional 1x1 projection shortcut (+BN for "original").
 The block is composed of the same sub-layers as the reference (so weights()/JSON line up); the executor fuses
-the residual add + ReLU into the last normalisation kernel (resnet.py:109-113)."""
+the residual add + ReLU into the last normalisation kernel (resnet.py:109-113). With sigmoid / tanh / elu / softplus nothing is
+fused: the inner `BN A` pairs run as batch norm + activation pass, the exit of an `original` block as the plain last batch
+norm followed by ops.add_act (act(x + y) in one pass, csrc/activation.hip), and inference takes the unfolded path."""
 from . import AbstractLayer, Act, InitialLayer
-from .activation import ActivationLayer
+from .activation import ActivationLayer, RELU_NAMES, check_activation
 from .batch_norm import BatchNormLayer
 from .batch_norm_relu import BatchNormReluLayer
 from .convolution import ConvLayer
@@ -21,7 +23,7 @@ class ResnetLayer(AbstractLayer):
         self.stride = tuple(json_param.get("stride", stride))
         self.bottleneck = json_param.get("bottleneck", bottleneck)
         self.version = json_param.get("version", version)
-        self.activation = json_param.get("activation", activation)
+        self.activation = check_activation(json_param.get("activation", activation))
         self.bn_json_param = json_param.get("bnParam", {"enabled": json_param.get("enableBatchNorm", True)})
 
         fs = self.filter_shape
@@ -122,10 +124,15 @@ class ResnetLayer(AbstractLayer):
     def _shortcut(self):
         return self.layers[self.n_main:]
 
+    def _smooth_exit(self):
+        """an `original` block whose exit activation is none of the ReLUs the last batch norm's passes can take in: that batch
+        norm runs plain, ops.add_act writes the block's output from its output and the shortcut (csrc/activation.hip)"""
+        return "pre-activation" not in self.version and self.activation != "none" and self.activation not in RELU_NAMES
+
     def _fold_plan(self):
         """inference: [(conv, bn, relu, output tensor or None)] of the main path and of the shortcut when every batch norm sits directly behind
         a convolution (the `original` blocks with fused BN-ReLU), else None"""
-        if "pre-activation" in self.version or not self.bn_json_param.get("enabled", True):
+        if "pre-activation" in self.version or not self.bn_json_param.get("enabled", True) or self._smooth_exit():
             return None
         main, sc = self._main(), self._shortcut()
 
@@ -159,8 +166,7 @@ class ResnetLayer(AbstractLayer):
             for conv, bn, relu, oa in ps:
                 conv.forward_folded(ctx, bn, relu=relu, out_act=oa)
             res = ps[-1][1].output.data if ps else self.input.data
-            relu = self.activation in ("relu", "relu-safe")
-            assert relu or self.activation == "none", self.activation
+            relu = self.activation in RELU_NAMES
             pm[-1][0].forward_folded(ctx, pm[-1][1], add=res, relu=relu, out_act=self.output)
             return
         main, sc = self._main(), self._shortcut()
@@ -173,16 +179,23 @@ class ResnetLayer(AbstractLayer):
             # output = x + y : the add rides in the last convolution's epilogue
             main[-1].forward(ctx, add=res)
             self.output.data = main[-1].output.data
+        elif self._smooth_exit():
+            main[-1].forward(ctx, relu=False)
+            self.output.data = ops.add_act(main[-1].output.data, res, self.output_shape[1], self.activation)
         else:
-            relu = self.activation in ("relu", "relu-safe")
-            assert relu or self.activation == "none", self.activation
-            main[-1].forward(ctx, res=res, relu=relu, out_act=self.output)
+            main[-1].forward(ctx, res=res, relu=self.activation in RELU_NAMES, out_act=self.output)
 
     def backward(self, ctx):
         main, sc = self._main(), self._shortcut()
         if "pre-activation" in self.version:
             dres = self.output.grad
             main[-1].output.grad = self.output.grad
+            main[-1].backward(ctx)
+        elif self._smooth_exit():
+            # the gradient of the sum: what the last batch norm receives and what the shortcut receives
+            from .. import ops
+            dres = ops.act_bwd(self.output.data, self.output.grad, self.output_shape[1], self.activation)
+            main[-1].output.grad = dres
             main[-1].backward(ctx)
         else:
             dres = main[-1].backward(ctx, want_dres=True)

@@ -140,6 +140,9 @@ SIGNATURES = {
     "denet_add": (I, [P, P, P, L, I, P]),
     "denet_relu_fwd": (I, [P, P, L, P]),
     "denet_relu_bwd": (I, [P, P, P, L, P]),
+    "denet_act_fwd": (I, [P, P, L, I, I, I, P]),
+    "denet_act_bwd": (I, [P, P, P, L, I, I, I, P]),
+    "denet_add_act_fwd": (I, [P, P, P, L, I, I, I, P]),
     "denet_colsum_workspace_bytes": (Z, [L, I]),
     "denet_colsum": (I, [P, P, P, L, I, P]),
     "denet_solver_step": (I, [P, P, P, L, L, F, F, I, F, F, I, P]),

@@ -132,9 +132,18 @@ def merge_splits(model):
 
 def set_activation(model, activation):
     """modify.py:48-51: every activation / residual layer takes the activation named on the command line"""
+    from ..layer.activation import check_activation
+    check_activation(activation)
     j = model.export_json()
     changed = False
-    for l in j["layers"]:
+    for index, l in enumerate(j["layers"]):
+        if l["type"] == "resnet" and "bnrelu" in l["version"] and activation != "relu" and l.get("activation") != activation:
+            # a block converted by --convert-bn-relu stores `batchnorm-relu` sub-layers; with any other activation the block is
+            # built from `batchnorm` + `activation` sub-layers and the stored ones no longer line up (the reference dies on the
+            # same mismatch when it reloads)
+            raise ValueError("--activation %s: layer %i is a residual block converted by --convert-bn-relu (version '%s', fused "
+                             "batchnorm-relu sub-layers), which only 'relu' can run; set the activation before converting"
+                             % (activation, index + 1, l["version"]))
         if l["type"] in ("activation", "resnet") and l.get("activation") != activation:
             l["activation"] = activation
             changed = True

@@ -1800,6 +1800,38 @@ def relu_bwd(y, dy):
     return dx
 
 
+# the smooth activations of csrc/activation.hip: name -> DENET_ACT_* (include/denet_hip.h)
+ACT_KINDS = {"sigmoid": 1, "tanh": 2, "elu": 3, "softplus": 4}
+
+
+def act_fwd(x, c_logical, kind):
+    """y = act(x) over the first c_logical channels of a channel-padded NHWC tensor, +0 in the padding channels"""
+    CP = x.shape[-1]
+    y = torch.empty_like(x)
+    check(_L().denet_act_fwd(ptr(x), ptr(y), x.numel() // CP, int(c_logical), CP, ACT_KINDS[kind], stream_ptr()), "act_fwd")
+    return y
+
+
+def act_bwd(y, dy, c_logical, kind):
+    """dx = dy * act'(x), written from the forward output y; +0 in the padding channels"""
+    CP = y.shape[-1]
+    assert y.shape == dy.shape, (tuple(y.shape), tuple(dy.shape))
+    dx = torch.empty_like(dy)
+    check(_L().denet_act_bwd(ptr(y), ptr(dy), ptr(dx), y.numel() // CP, int(c_logical), CP, ACT_KINDS[kind], stream_ptr()),
+          "act_bwd")
+    return dx
+
+
+def add_act(a, b, c_logical, kind):
+    """y = act(a + b) in one pass (the exit of an `original` residual block); backward: act_bwd, for both summands"""
+    CP = a.shape[-1]
+    assert a.shape == b.shape, (tuple(a.shape), tuple(b.shape))
+    y = torch.empty_like(a)
+    check(_L().denet_add_act_fwd(ptr(a), ptr(b), ptr(y), a.numel() // CP, int(c_logical), CP, ACT_KINDS[kind], stream_ptr()),
+          "add_act")
+    return y
+
+
 def colsum(x, out=None):
     C = x.shape[-1]
     M = x.numel() // C

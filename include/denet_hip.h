@@ -31,6 +31,10 @@ typedef struct ihipStream_t* hipStream_t;
 #define DENET_ERR_ARG (-1000)
 #define DENET_TAP_THEANO 0 /* denet/layer/denet_sparse.py:72-84  (i*extent)/(gs-1), round half to even */
 #define DENET_TAP_CUDA 1   /* denet/layer/denet_sparse_op.py:65-71 i*extent*(1/(gs-1)), lroundf           */
+#define DENET_ACT_SIGMOID 1  /* denet/layer/activation.py:28-29 */
+#define DENET_ACT_TANH 2     /* denet/layer/activation.py:37-38 */
+#define DENET_ACT_ELU 3      /* denet/layer/activation.py:35-36 (alpha = 1) */
+#define DENET_ACT_SOFTPLUS 4 /* denet/layer/activation.py:41-42 */
 #define DENET_SOLVER_SGD 0      /* denet/model/model_cnn.py:282-287 */
 #define DENET_SOLVER_NESTEROV 1 /* denet/model/model_cnn.py:289-294 ("torch" == "nesterov") */
 
@@ -513,6 +517,17 @@ int denet_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, int
 int denet_add(const float* a, const float* b, float* y, long n, int relu, hipStream_t stream);
 int denet_relu_fwd(const float* x, float* y, long n, hipStream_t stream);
 int denet_relu_bwd(const float* y, const float* dy, float* dx, long n, hipStream_t stream);
+/* the smooth `A` activations (denet/layer/activation.py:25-44), kind = DENET_ACT_*. x / y / dy / dx are [M][CP] with C logical
+ * channels (M = batch x pixels); channels C..CP-1 of every output are written as +0.0f whatever the inputs hold there
+ * (f(0) != 0 for sigmoid and softplus). No finite x gives NaN or Inf.
+ *   act_fwd      y = act(x)                          tensor.nnet.sigmoid :29, nnet.elu :36, tensor.tanh :38, nnet.softplus :42
+ *   act_bwd      dx = dy * act'(x), written from the forward output y (sigmoid y(1-y), tanh 1-y^2, elu y>0 ? 1 : y+1,
+ *                softplus -expm1(-y)): what theano.grad derives for the four calls above
+ *   add_act_fwd  y = act(a + b): the exit of an `original` residual block, denet/layer/resnet.py:113 apply(x + y, activation);
+ *                its backward pass is act_bwd, the result is the gradient of both summands                                   */
+int denet_act_fwd(const float* x, float* y, long M, int C, int CP, int kind, hipStream_t stream);
+int denet_act_bwd(const float* y, const float* dy, float* dx, long M, int C, int CP, int kind, hipStream_t stream);
+int denet_add_act_fwd(const float* a, const float* b, float* y, long M, int C, int CP, int kind, hipStream_t stream);
 size_t denet_colsum_workspace_bytes(long M, int C);
 int denet_colsum(const float* x, float* out, void* workspace, long M, int C, hipStream_t stream);
 int denet_solver_step(float* params, float* moments, const float* grads, long n, long n_decay, float lr,
