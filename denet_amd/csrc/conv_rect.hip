@@ -1,0 +1,535 @@
+// Convolution with a per-axis geometry for gfx950 (MI355X): the `C.X[k, kh, kw, sh, sw]` / `DC.X[...]` tokens of the model
+// description (reference: denet/layer/convolution.py:55-83,99-112, deconvolution.py:54-65; gradients: tensor.grad,
+// model_cnn.py:318). Filter R x S, stride (sh, sw), padding (ph, pw), output OH x OW given by the caller. The square kernels
+// of igemm.hip / winograd.hip take ONE stride and ONE pad; this file is the direct kernel of everything else and shares no
+// code path with them.
+//
+// Layout (HBM):   activations NHWC fp32, filters KRSC fp32 correlation taps (as igemm.hip).
+// Arithmetic:     v_mfma_f32_32x32x2_f32, exact fp32 FMA chain, accumulators in registers.
+// Tiling:         256 threads (4 wave64) per BM x BN output tile, the reduction walked in chunks of 32 through two LDS
+//                 buffers (the next chunk travels global -> VGPR while the current one is multiplied; one barrier per chunk).
+//                 LDS layouts as igemm.hip: K-inner [rows][32+4] (ds_read_b128), K-outer [32][cols+4] (ds_read_b32).
+//                   fwd:   A = im2col(x) K-inner,           B = w K-inner
+//                   dgrad: A = im2col(dy) K-inner,          B = w (per tap) K-outer; grid.y = the sh*sw classes of input pixels
+//                   wgrad: A = dy K-outer (rows = k),       B = im2col(x) K-outer; grid.y = slices of the pixel reduction,
+//                          added in slice order by a second kernel (deterministic, no atomics)
+//                 Inside an 8-wide k block lane-half h consumes k = 4h..4h+3 of both operands (a fixed permutation of the sum).
+// One tile table, chosen by the channel counts alone: no measured choice, the same kernel in every process.
+#include "common.h"
+#include "../../include/denet_hip.h"
+
+namespace {
+
+constexpr int BK = 32;
+constexpr int LDK = BK + 4;
+
+enum { PASS_FWD = 0, PASS_DGRAD = 1, PASS_WGRAD = 2 };
+
+struct RectParams {
+    const float* a;      // fwd: x   dgrad: dy  wgrad: dy
+    const float* b;      // fwd: w   dgrad: w   wgrad: x
+    float* out;          // fwd: y   dgrad: dx  wgrad: dw or the slices
+    const float* bias;   // fwd, [K] or null
+    const float* add;    // fwd / dgrad: tensor of the output's shape added in the epilogue, or null
+    int relu;            // fwd: max(., 0) after bias and add
+    int N, H, W, C;
+    int OH, OW, K;
+    int R, S, S_real;
+    int sh, sw, shs, sws, ph, pw;   // strides, their log2, padding
+    int M, NC;           // GEMM rows / columns
+    int ksteps;          // fwd / wgrad: 32-wide reduction chunks
+    int steps_per_split;
+    long split_stride;   // wgrad: elements between slices
+    int tiles_m, tiles_n;
+    int npix;            // N*OH*OW
+    int Hc, Wc;          // dgrad: ceil(H/sh), ceil(W/sw): rows of one class per image (classes with fewer are masked)
+    FastDiv div_img;     // fwd / wgrad: OH*OW   dgrad: Hc*Wc
+    FastDiv div_row;     // fwd / wgrad: OW      dgrad: Wc
+    unsigned a_bytes, b_bytes;   // extents of a / b: lanes outside read 0 through the buffer descriptor
+};
+
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+constexpr int OOB_OFFSET = (int)0xF0000000u;   // beyond every extent check_rect admits
+__device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, int elem_off, bool ok) {
+    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, ok ? elem_off * 4 : OOB_OFFSET, 0, 0);
+    return __builtin_bit_cast(f32x4, v);
+}
+
+template <int PASS, int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
+    constexpr bool A_KIN = (PASS != PASS_WGRAD);
+    constexpr bool B_KIN = (PASS == PASS_FWD);
+    constexpr int TM = BM / (32 * WM);
+    constexpr int TN = BN / (32 * WN);
+    static_assert(WM * WN == 4, "4 waves per workgroup");
+    static_assert(TM >= 1 && TN >= 1, "tile too small");
+    constexpr int LDA = BM + 4, LDB = BN + 4;         // K-outer rows
+    constexpr int SZA = A_KIN ? BM * LDK : BK * LDA;
+    constexpr int SZB = B_KIN ? BN * LDK : BK * LDB;
+    constexpr int PA = BM / 32, PB = BN / 32;          // loader passes, one float4 per thread each
+    constexpr int LPR_A = BM / 4, RPP_A = 256 / LPR_A;
+    constexpr int LPR_B = BN / 4, RPP_B = 256 / LPR_B;
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* sA = smem;              // [2][SZA]
+    float* sB = smem + 2 * SZA;    // [2][SZB]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wm = wave / WN, wn = wave % WN;
+    const int li = lane & 31, lh = lane >> 5;
+
+    const uint32_t tile_id = xcd_remap(blockIdx.x, gridDim.x);
+    const int tile_n = tile_id % p.tiles_n;
+    const int tile_m = tile_id / p.tiles_n;
+    const int m0 = tile_m * BM, n0 = tile_n * BN;
+
+    // dgrad: grid.y = class (py, px) of input pixels iy = ya*sh + py, ix = xa*sw + px. Such a pixel receives the taps
+    // r = r0 + sh*r', s = s0 + sw*s' only, from the output pixel (ya + by - r', xa + bx - s'): a dense problem per class
+    int dg_py = 0, dg_px = 0, dg_r0 = 0, dg_s0 = 0, dg_rc = 0, dg_sc = 0, dg_by = 0, dg_bx = 0;
+    int step_begin = 0, step_end = p.ksteps;
+    if (PASS == PASS_DGRAD) {
+        dg_py = blockIdx.y >> p.sws;
+        dg_px = blockIdx.y & (p.sw - 1);
+        dg_r0 = (dg_py + p.ph) & (p.sh - 1);
+        dg_s0 = (dg_px + p.pw) & (p.sw - 1);
+        dg_by = (dg_py + p.ph) >> p.shs;
+        dg_bx = (dg_px + p.pw) >> p.sws;
+        dg_rc = (p.R > dg_r0) ? ((p.R - dg_r0 + p.sh - 1) >> p.shs) : 0;
+        dg_sc = (p.S_real > dg_s0) ? ((p.S_real - dg_s0 + p.sw - 1) >> p.sws) : 0;
+        step_end = dg_rc * dg_sc * (p.K / BK);
+    } else if (PASS == PASS_WGRAD) {
+        step_begin = blockIdx.y * p.steps_per_split;
+        step_end = min(p.ksteps, step_begin + p.steps_per_split);
+    }
+    const int nsteps = step_end - step_begin;
+
+    // ---------------- per-thread loader state ----------------
+    const int q8 = tid & 7, row8 = tid >> 3;             // K-inner: float4 column of the chunk, row of a 32-row pass
+    const int qa = tid % LPR_A, kra = tid / LPR_A;       // K-outer A
+    const int qb = tid % LPR_B, krb = tid / LPR_B;       // K-outer B
+    // fewer than 32 channels (the network input): a chunk spans 32 / C taps of one filter row
+    const int qs = (PASS == PASS_FWD && p.C < 32) ? (4 * q8) / p.C : 0;
+    const int qc = (PASS == PASS_FWD && p.C < 32) ? (4 * q8) % p.C : 4 * q8;
+
+    int a_off[PA], a_y[PA], a_x[PA];
+    int b_off[PB];
+    bool b_ok[PB];
+    int wg_r = 0, wg_s = 0, wg_c = 0;
+    bool wg_colok = false;
+    const int rsc = p.R * p.S * p.C;
+
+    if (PASS == PASS_FWD) {
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            const int m = m0 + row8 + 32 * i;
+            a_y[i] = -(p.R + 1); a_x[i] = 0; a_off[i] = 0;      // a row that is none: every tap lies above the image
+            if (m < p.M) {
+                const uint32_t n = p.div_img.div(m);
+                const uint32_t rem = m - n * (p.OH * p.OW);
+                const uint32_t oy = p.div_row.div(rem);
+                const uint32_t ox = rem - oy * p.OW;
+                a_y[i] = (int)oy * p.sh - p.ph;
+                a_x[i] = (int)ox * p.sw - p.pw + qs;
+                a_off[i] = (((int)n * p.H + a_y[i]) * p.W + a_x[i]) * p.C + qc;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+            const int n = n0 + row8 + 32 * i;
+            b_ok[i] = n < p.K;
+            b_off[i] = n * rsc + 4 * q8;
+        }
+    } else if (PASS == PASS_DGRAD) {
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            const int m = m0 + row8 + 32 * i;
+            a_y[i] = -1; a_x[i] = 0; a_off[i] = 0;              // a row that is none: every tap comes from above the output
+            if (m < p.M) {
+                const uint32_t n = p.div_img.div(m);
+                const uint32_t rem = m - n * (p.Hc * p.Wc);
+                const uint32_t ya = p.div_row.div(rem);
+                const uint32_t xa = rem - ya * p.Wc;
+                if ((int)ya * p.sh + dg_py < p.H && (int)xa * p.sw + dg_px < p.W) {
+                    a_y[i] = (int)ya + dg_by;
+                    a_x[i] = (int)xa + dg_bx;
+                    a_off[i] = (int)n * (p.OH * p.OW * p.K) + 4 * q8;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+            const int col = n0 + 4 * qb;
+            b_ok[i] = col < p.C;
+            b_off[i] = (krb + RPP_B * i) * rsc + col;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            a_off[i] = (kra + RPP_A * i) * p.K + m0 + 4 * qa;
+            a_y[i] = 0; a_x[i] = 0;
+        }
+        const int jg = n0 + 4 * qb;
+        const int rs = jg / p.C;
+        wg_c = jg - rs * p.C;
+        wg_r = rs / p.S;
+        wg_s = rs - wg_r * p.S;
+        wg_colok = (jg < p.NC) && (wg_s < p.S_real);
+#pragma unroll
+        for (int i = 0; i < PB; ++i) { b_ok[i] = wg_colok; b_off[i] = 0; }
+    }
+    const bool wg_rowok = (PASS == PASS_WGRAD) ? (m0 + 4 * qa < p.K) : true;
+
+    const __amdgpu_buffer_rsrc_t r_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.b, 0, p.b_bytes, 0x00020000);
+
+    // wave-uniform reduction cursor: fwd (r, s, c0) over the filter, dgrad (r', s', k0) over the taps of the class; wgrad: chunk
+    int cur_r = 0, cur_s = 0, cur_c = 0, cur_step = step_begin;
+    f32x4 ra[PA], rb[PB];
+
+    auto load_chunk = [&]() {
+        if (PASS == PASS_FWD) {
+            const int u_off = (cur_r * p.W + cur_s) * p.C + cur_c;
+            const bool tap_ok = cur_s + qs < p.S_real;
+#pragma unroll
+            for (int i = 0; i < PA; ++i) {
+                const bool ok = tap_ok && ((unsigned)(a_y[i] + cur_r) < (unsigned)p.H) && ((unsigned)(a_x[i] + cur_s) < (unsigned)p.W);
+                ra[i] = buf_load4(r_a, a_off[i] + u_off, ok);
+            }
+#pragma unroll
+            for (int i = 0; i < PB; ++i) rb[i] = buf_load4(r_b, b_off[i] + cur_step * BK, b_ok[i]);
+            if (p.C >= 32) {
+                cur_c += BK;
+                if (cur_c >= p.C) {
+                    cur_c = 0;
+                    if (++cur_s >= p.S) { cur_s = 0; ++cur_r; }
+                }
+            } else {
+                cur_s += 32 / p.C;
+                if (cur_s >= p.S) { cur_s = 0; ++cur_r; }
+            }
+        } else if (PASS == PASS_DGRAD) {
+#pragma unroll
+            for (int i = 0; i < PA; ++i) {
+                const int oy = a_y[i] - cur_r, ox = a_x[i] - cur_s;
+                const bool ok = ((unsigned)oy < (unsigned)p.OH) && ((unsigned)ox < (unsigned)p.OW);
+                ra[i] = buf_load4(r_a, a_off[i] + (oy * p.OW + ox) * p.K + cur_c, ok);
+            }
+            const int u_offb = cur_c * rsc + ((dg_r0 + (cur_r << p.shs)) * p.S + dg_s0 + (cur_s << p.sws)) * p.C;
+#pragma unroll
+            for (int i = 0; i < PB; ++i) rb[i] = buf_load4(r_b, b_off[i] + u_offb, b_ok[i]);
+            cur_c += BK;
+            if (cur_c >= p.K) {
+                cur_c = 0;
+                if (++cur_s >= dg_sc) { cur_s = 0; ++cur_r; }
+            }
+        } else {
+            const int pix0 = cur_step * BK;
+#pragma unroll
+            for (int i = 0; i < PA; ++i) {
+                const bool ok = wg_rowok && (pix0 + kra + RPP_A * i < p.npix);
+                ra[i] = buf_load4(r_a, pix0 * p.K + a_off[i], ok);
+            }
+#pragma unroll
+            for (int i = 0; i < PB; ++i) {
+                const int pix = pix0 + krb + RPP_B * i;
+                const uint32_t n = p.div_img.div(pix);
+                const uint32_t rem = pix - n * (p.OH * p.OW);
+                const uint32_t oy = p.div_row.div(rem);
+                const uint32_t ox = rem - oy * p.OW;
+                const int iy = (int)oy * p.sh - p.ph + wg_r;
+                const int ix = (int)ox * p.sw - p.pw + wg_s;
+                const bool ok = wg_colok && (pix < p.npix) && ((unsigned)iy < (unsigned)p.H) && ((unsigned)ix < (unsigned)p.W);
+                rb[i] = buf_load4(r_b, (((int)n * p.H + iy) * p.W + ix) * p.C + wg_c, ok);
+            }
+        }
+        ++cur_step;
+    };
+
+    auto store_chunk = [&](int buf) {
+        float* da = sA + buf * SZA;
+        float* db = sB + buf * SZB;
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            if (A_KIN) *(f32x4*)(da + (row8 + 32 * i) * LDK + 4 * q8) = ra[i];
+            else *(f32x4*)(da + (kra + RPP_A * i) * LDA + 4 * qa) = ra[i];
+        }
+#pragma unroll
+        for (int i = 0; i < PB; ++i) {
+            if (B_KIN) *(f32x4*)(db + (row8 + 32 * i) * LDK + 4 * q8) = rb[i];
+            else *(f32x4*)(db + (krb + RPP_B * i) * LDB + 4 * qb) = rb[i];
+        }
+    };
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+
+    const int arow = wm * (TM * 32) + li;     // this lane's row of A / row (column of the product) of B inside the tile
+    const int brow = wn * (TN * 32) + li;
+
+    if (nsteps > 0) {
+        load_chunk();
+        store_chunk(0);
+    }
+    __syncthreads();
+    for (int st = 0; st < nsteps; ++st) {
+        const bool more = st + 1 < nsteps;
+        if (more) load_chunk();
+        const float* ca = sA + (st & 1) * SZA;
+        const float* cb = sB + (st & 1) * SZB;
+#pragma unroll
+        for (int kb = 0; kb < BK / 8; ++kb) {
+            f32x4 av[TM], bv[TN];
+            const int k0 = 8 * kb + 4 * lh;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                if (A_KIN) {
+                    av[i] = *(const f32x4*)(ca + (arow + 32 * i) * LDK + k0);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) av[i][t] = ca[(k0 + t) * LDA + arow + 32 * i];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                if (B_KIN) {
+                    bv[j] = *(const f32x4*)(cb + (brow + 32 * j) * LDK + k0);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) bv[j][t] = cb[(k0 + t) * LDB + brow + 32 * j];
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j][t], av[i][t], acc[i][j], 0, 0, 0);
+        }
+        if (more) store_chunk((st + 1) & 1);
+        __syncthreads();
+    }
+
+    // ---------------- epilogue: the lane owns row m = ..+li, columns 8g + 4h .. +3 in registers 4g .. 4g+3 ----------------
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int m = m0 + arow + 32 * i;
+        long row = -1;
+        if (PASS == PASS_FWD) {
+            if (m < p.M) row = (long)m * p.K;
+        } else if (PASS == PASS_DGRAD) {
+            if (m < p.M) {
+                const uint32_t n = p.div_img.div(m);
+                const uint32_t rem = m - n * (p.Hc * p.Wc);
+                const uint32_t ya = p.div_row.div(rem);
+                const uint32_t xa = rem - ya * p.Wc;
+                const int iy = (int)ya * p.sh + dg_py, ix = (int)xa * p.sw + dg_px;
+                if (iy < p.H && ix < p.W) row = (((long)n * p.H + iy) * p.W + ix) * p.C;
+            }
+        } else {
+            if (m < p.K) row = (long)blockIdx.y * p.split_stride + (long)m * p.NC;
+        }
+        if (row < 0) continue;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = n0 + wn * (TN * 32) + 32 * j + 8 * g + 4 * lh;
+                if (n >= p.NC) continue;
+                f32x4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+                if (PASS == PASS_FWD && p.bias) v += *(const f32x4*)(p.bias + n);
+                if (PASS != PASS_WGRAD && p.add) v += *(const f32x4*)(p.add + row + n);
+                if (PASS == PASS_FWD && p.relu) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
+                }
+                *(f32x4*)(p.out + row + n) = v;
+            }
+        }
+    }
+}
+
+// dw = the slices added in slice order (one float4 column per thread)
+__global__ __launch_bounds__(256) void conv_rect_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, long n4,
+                                                               int splits) {
+    const long col = (long)blockIdx.x * 256 + threadIdx.x;
+    if (col >= n4) return;
+    const f32x4* w4 = (const f32x4*)ws;
+    f32x4 s = w4[col];
+    for (int z = 1; z < splits; ++z) s += w4[col + (long)z * n4];
+    ((f32x4*)out)[col] = s;
+}
+
+int ilog2_exact(int v) {
+    if (v <= 0) return -1;
+    int s = 0;
+    while ((1 << s) < v) s++;
+    return ((1 << s) == v) ? s : -1;
+}
+
+int check_rect(const char* who, int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
+               int OW) {
+    DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "%s: non-positive dimension", who);
+    DENET_CHECK_ARG(S_real > 0 && S_real <= S, "%s: S_real (%d) out of range", who, S_real);
+    DENET_CHECK_ARG(ilog2_exact(sh) >= 0, "%s: row stride sh must be a power of two (got %d)", who, sh);
+    DENET_CHECK_ARG(ilog2_exact(sw) >= 0, "%s: column stride sw must be a power of two (got %d)", who, sw);
+    DENET_CHECK_ARG(ph >= 0 && pw >= 0, "%s: negative padding (ph %d, pw %d)", who, ph, pw);
+    DENET_CHECK_ARG(K % 32 == 0, "%s: physical K (%d) must be a multiple of 32", who, K);
+    if (C >= 32) {
+        DENET_CHECK_ARG(C % 32 == 0, "%s: physical C (%d) must be a multiple of 32", who, C);
+        DENET_CHECK_ARG(S_real == S, "%s: S_real (%d) != S (%d) with 32 channels or more", who, S_real, S);
+    } else {
+        DENET_CHECK_ARG(C == 4 || C == 8 || C == 16, "%s: small C must be 4, 8 or 16 (got %d)", who, C);
+        DENET_CHECK_ARG((S * C) % 32 == 0, "%s: S*C (%d) must be a multiple of 32 for small C", who, S * C);
+    }
+    DENET_CHECK_ARG(H + 2 * ph >= R && OH > 0 && (H + 2 * ph - R) / sh + 1 >= OH, "%s: OH=%d inconsistent", who, OH);
+    DENET_CHECK_ARG(W + 2 * pw >= S_real && OW > 0 && (W + 2 * pw - S_real) / sw + 1 >= OW, "%s: OW=%d inconsistent", who, OW);
+    // 32-bit buffer descriptors (byte offsets); 0xF0000000 marks a lane that reads nothing. The padded class grid of the
+    // data gradient (ceil(H/sh)*sh x ceil(W/sw)*sw) is indexed with 32-bit integers as well
+    DENET_CHECK_ARG((long)N * (H + sh) * (W + sw) * C * 4 < 0xF0000000L && (long)N * OH * OW * K * 4 < 0xF0000000L &&
+                        (long)K * R * S * C * 4 < 0xF0000000L,
+                    "%s: tensor exceeds the 32-bit buffer extent (3.75 GiB)", who);
+    return DENET_OK;
+}
+
+RectParams make_params(int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW) {
+    RectParams p = {};
+    p.N = N; p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.K = K; p.R = R; p.S = S; p.S_real = S_real;
+    p.sh = sh; p.sw = sw; p.shs = ilog2_exact(sh); p.sws = ilog2_exact(sw); p.ph = ph; p.pw = pw;
+    p.npix = N * OH * OW;
+    return p;
+}
+
+template <int PASS, int BM, int BN, int WM, int WN>
+int launch_rect(RectParams& p, unsigned grid_y, hipStream_t stream) {
+    constexpr bool A_KIN = (PASS != PASS_WGRAD);
+    constexpr bool B_KIN = (PASS == PASS_FWD);
+    constexpr int SZA = A_KIN ? BM * LDK : BK * (BM + 4);
+    constexpr int SZB = B_KIN ? BN * LDK : BK * (BN + 4);
+    constexpr size_t lds = 2 * (size_t)(SZA + SZB) * sizeof(float);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)conv_rect_kernel<PASS, BM, BN, WM, WN>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            denet_set_error("conv_rect: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+            return -(int)e;
+        }
+        attr_set = true;
+    }
+    p.tiles_m = ceil_div(p.M, BM);
+    p.tiles_n = ceil_div(p.NC, BN);
+    const int prof = denet_prof_begin(20, PASS, BM, BN, stream);       // ops.kernel_symbol: conv_rect_kernel<PASS, BM, BN>
+    hipLaunchKernelGGL((conv_rect_kernel<PASS, BM, BN, WM, WN>), dim3((unsigned)(p.tiles_m * p.tiles_n), grid_y, 1), dim3(256), lds,
+                       stream, p);
+    denet_prof_end(prof, stream);
+    DENET_CHECK_LAUNCH("conv_rect");
+    return DENET_OK;
+}
+
+// rows of 128 pixels against 128 / 64 / 32 output columns (fwd, dgrad)
+template <int PASS>
+int launch_by_cols(RectParams& p, unsigned grid_y, hipStream_t stream) {
+    if (p.NC >= 96) return launch_rect<PASS, 128, 128, 2, 2>(p, grid_y, stream);
+    if (p.NC >= 64) return launch_rect<PASS, 128, 64, 2, 2>(p, grid_y, stream);
+    return launch_rect<PASS, 128, 32, 4, 1>(p, grid_y, stream);
+}
+
+// slices of the filter gradient's pixel reduction: enough workgroups for two per CU, at least 4 chunks each, at most 128
+int wgrad_splits(int N, int C, int K, int R, int S, int OH, int OW) {
+    const int bm = K >= 96 ? 128 : (K >= 64 ? 64 : 32);
+    const long tiles = (long)ceil_div(K, bm) * ceil_div((long)R * S * C, 128);
+    const int ksteps = ceil_div((long)N * OH * OW, BK);
+    long sp = 512 / tiles;
+    if (sp > ksteps / 4) sp = ksteps / 4;
+    if (sp > 128) sp = 128;
+    if (sp < 1) sp = 1;
+    const int per = ceil_div(ksteps, sp);
+    return ceil_div(ksteps, per);
+}
+
+}  // namespace
+
+extern "C" int denet_conv_rect_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
+                                   int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
+                                   int OW, hipStream_t stream) {
+    int rc = check_rect("conv_rect_fwd", N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    if (rc) return rc;
+    DENET_CHECK_ARG(x && w && y, "conv_rect_fwd: null tensor");
+    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    p.a = x; p.b = w; p.out = y; p.bias = bias; p.add = add; p.relu = relu;
+    p.M = p.npix; p.NC = K;
+    p.ksteps = R * S * C / BK;
+    p.div_img.init((uint32_t)(OH * OW));
+    p.div_row.init((uint32_t)OW);
+    p.a_bytes = (unsigned)((long)N * H * W * C * 4);
+    p.b_bytes = (unsigned)((long)K * R * S * C * 4);
+    return launch_by_cols<PASS_FWD>(p, 1, stream);
+}
+
+extern "C" int denet_conv_rect_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
+                                     int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
+                                     hipStream_t stream) {
+    int rc = check_rect("conv_rect_dgrad", N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    if (rc) return rc;
+    DENET_CHECK_ARG(dy && w && dx, "conv_rect_dgrad: null tensor");
+    DENET_CHECK_ARG(C % 32 == 0, "conv_rect_dgrad: physical C (%d) must be a multiple of 32 (the network input has no gradient)", C);
+    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    p.a = dy; p.b = w; p.out = dx; p.add = add;
+    p.Hc = ceil_div(H, sh); p.Wc = ceil_div(W, sw);
+    p.M = N * p.Hc * p.Wc; p.NC = C;
+    p.div_img.init((uint32_t)(p.Hc * p.Wc));
+    p.div_row.init((uint32_t)p.Wc);
+    p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
+    p.b_bytes = (unsigned)((long)K * R * S * C * 4);
+    return launch_by_cols<PASS_DGRAD>(p, (unsigned)(sh * sw), stream);
+}
+
+extern "C" size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int R, int S, int OH, int OW) {
+    if (N <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || OH <= 0 || OW <= 0) return 0;
+    const int sp = wgrad_splits(N, C, K, R, S, OH, OW);
+    return sp > 1 ? (size_t)sp * K * R * S * C * sizeof(float) : 0;
+}
+
+extern "C" int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N,
+                                     int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
+                                     int OW, hipStream_t stream) {
+    int rc = check_rect("conv_rect_wgrad", N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    if (rc) return rc;
+    DENET_CHECK_ARG(x && dy && dw, "conv_rect_wgrad: null tensor");
+    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    p.a = dy; p.b = x;
+    p.M = K; p.NC = R * S * C;
+    p.ksteps = ceil_div(p.npix, BK);
+    const int splits = wgrad_splits(N, C, K, R, S, OH, OW);
+    p.steps_per_split = ceil_div(p.ksteps, splits);
+    p.split_stride = (long)K * p.NC;
+    if (splits > 1) {
+        DENET_CHECK_ARG(workspace && workspace_bytes >= (size_t)splits * p.split_stride * sizeof(float),
+                        "conv_rect_wgrad: workspace of %zu bytes, %zu needed (denet_conv_rect_wgrad_workspace_bytes)", workspace_bytes,
+                        (size_t)splits * p.split_stride * sizeof(float));
+        p.out = workspace;
+    } else {
+        p.out = dw;
+    }
+    p.div_img.init((uint32_t)(OH * OW));
+    p.div_row.init((uint32_t)OW);
+    p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
+    p.b_bytes = (unsigned)((long)N * H * W * C * 4);
+    if (K >= 96) rc = launch_rect<PASS_WGRAD, 128, 128, 2, 2>(p, (unsigned)splits, stream);
+    else if (K >= 64) rc = launch_rect<PASS_WGRAD, 64, 128, 2, 2>(p, (unsigned)splits, stream);
+    else rc = launch_rect<PASS_WGRAD, 32, 128, 1, 4>(p, (unsigned)splits, stream);
+    if (rc) return rc;
+    if (splits > 1) {
+        const long n4 = p.split_stride / 4;
+        hipLaunchKernelGGL(conv_rect_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, workspace, dw, n4, splits);
+        DENET_CHECK_LAUNCH("conv_rect_reduce");
+    }
+    return DENET_OK;
+}

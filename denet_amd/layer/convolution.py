@@ -30,6 +30,14 @@ def conv_padding(border_mode, k):
     raise Exception("Unknown border mode: " + str(border_mode))
 
 
+def conv_padding2(border_mode, r, s):
+    """(rows, columns) of zero padding for an r x s filter (convolution.py:55-80 works the border modes out per axis): the named
+    modes pad each axis by its own filter extent, an integer n pads (n, n), a pair is taken as given"""
+    if isinstance(border_mode, (tuple, list)):
+        return (int(border_mode[0]), int(border_mode[1]))
+    return (conv_padding(border_mode, r), conv_padding(border_mode, s))
+
+
 def same_crop(border_mode, k):
     """True when the output of conv_padding's symmetric padding loses its last row and column (`same`, even k)"""
     return border_mode == "same" and k % 2 == 0
@@ -78,9 +86,12 @@ class ConvLayer(AbstractLayer):
             w = numpy.zeros(shape=fs)
 
         assert fs[1] == self.input_shape[1], "filter channels %i != input channels %i" % (fs[1], self.input_shape[1])
-        assert self.stride[0] == self.stride[1], "only square strides are supported"
-        assert fs[2] == fs[3], "only square filters are supported"
-        self.pad = conv_padding(self.border_mode, fs[2])
+        # a layer whose filter, stride or padding differs between rows and columns (`C.X`, an `R` head behind a non-square map)
+        # runs the per-axis kernels of csrc/conv_rect.hip (ops.conv_rect_*) and carries its padding as a pair; a square layer keeps
+        # the scalar padding and every line of the square path (tuned decisions, Winograd, fused statistics)
+        pad2 = conv_padding2(self.border_mode, fs[2], fs[3])
+        self.anisotropic = fs[2] != fs[3] or self.stride[0] != self.stride[1] or pad2[0] != pad2[1]
+        self.pad = pad2 if self.anisotropic else pad2[0]
         if self.border_mode == "same":
             assert self.stride == (1, 1)
 
@@ -93,11 +104,11 @@ class ConvLayer(AbstractLayer):
             self.beta = Param(numpy.zeros((fs[0],)), "conv beta", "vector", (self.kp,))
 
         # output shape (convolution.py:55-74)
-        oh = int(math.ceil((self.input_shape[-2] + 2 * self.pad - fs[2] + 1) / self.stride[0]))
-        ow = int(math.ceil((self.input_shape[-1] + 2 * self.pad - fs[3] + 1) / self.stride[1]))
+        oh = int(math.ceil((self.input_shape[-2] + 2 * pad2[0] - fs[2] + 1) / self.stride[0]))
+        ow = int(math.ceil((self.input_shape[-1] + 2 * pad2[1] - fs[3] + 1) / self.stride[1]))
         # `same` with an even filter: the passes get the output size explicitly (ops.conv_geom's ohw), None = the derived one
         self.ohw = None
-        if same_crop(self.border_mode, fs[2]):
+        if same_crop(self.border_mode, fs[2]) or same_crop(self.border_mode, fs[3]):
             oh, ow = self.input_shape[-2], self.input_shape[-1]
             self.ohw = (oh, ow)
         self.output_shape = (self.input_shape[0], fs[0], oh, ow)
@@ -160,6 +171,14 @@ class ConvLayer(AbstractLayer):
 
     def forward(self, ctx, add=None):
         from . import get_train
+        if self.anisotropic:
+            # the direct per-axis kernel on the plain tensor: a pending input is written first (Act.data), no skip add or
+            # statistics in the epilogue - the layers behind run their own passes
+            self.output.data = ops.conv_rect_fwd(self.input.data, self._w(), bias=self.beta.dev if self.use_bias else None, add=add,
+                                                 stride=self.stride, pad=self.pad, s_real=self.filter_shape[3],
+                                                 logical=self._logical(), cache=self._cache(), ohw=self.ohw)
+            self.output.stats = None
+            return
         # the input may be the output of a batch norm whose pointwise pass is still pending (ops.BnLink): a Winograd pass runs it
         # inside its input transform; whatever path conv_fwd takes, the activation exists afterwards and is stored back
         link = self.input.take_pending_data()
@@ -233,6 +252,12 @@ class ConvLayer(AbstractLayer):
             w_f, b_f = ops.bn_fold(self._w(), self.beta.dev if self.use_bias else None, bn.omega.dev, bn.beta.dev,
                                    bn.mean.dev, bn.stdinv.dev, bn.eps)
             ent = cache["fold"] = (ops.WEIGHTS_VERSION, bn, w_f, b_f)
+        if self.anisotropic:
+            y = ops.conv_rect_fwd(self.input.data, ent[2], bias=ent[3], add=add, stride=self.stride, pad=self.pad,
+                                  s_real=self.filter_shape[3], logical=self._logical(), cache=cache, relu=relu, ohw=self.ohw)
+            self.output.data = y
+            (out_act if out_act is not None else bn.output).data = y
+            return y
         link = self.input.take_pending_data()
         if isinstance(link, ops.NchwLink):
             self.input.set_pending_data(link)          # (see forward: the first layer reads the planar batch)
@@ -250,7 +275,23 @@ class ConvLayer(AbstractLayer):
         (out_act if out_act is not None else bn.output).data = y
         return y
 
+    def _backward_rect(self, ctx):
+        """backward of an anisotropic layer: filter gradient on the second stream, bias gradient by column sums, data gradient"""
+        dy = self.output.grad
+        x = self.input.data
+        if self.enabled and self.omega.grad is not None:
+            with ops.wgrad_stream():
+                ops.conv_rect_wgrad(x, dy, self.omega.dev_shape, stride=self.stride, pad=self.pad, s_real=self.filter_shape[3],
+                                    out=self.omega.grad.view(self.omega.dev_shape), logical=self._logical(), ohw=self.ohw)
+                if self.use_bias:
+                    ops.colsum(dy.view(-1, self.kp), out=self.beta.grad)
+        if getattr(self.input, "requires_grad", True):
+            self.input.grad = ops.conv_rect_dgrad(dy, self._w(), tuple(x.shape), add=self.input.grad, stride=self.stride,
+                                                  pad=self.pad, s_real=self.filter_shape[3], logical=self._logical(), ohw=self.ohw)
+
     def backward(self, ctx):
+        if self.anisotropic:
+            return self._backward_rect(ctx)
         # (the first layer on the planar network input has no data gradient and reads the image as it is)
         planar = getattr(self, "_planar_x", None) if not getattr(self.input, "requires_grad", True) else None
         # an input that is the un-written output of a pool-inverse layer (ops.UpLink, see forward): the data gradient needs its shape

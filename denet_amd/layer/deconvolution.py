@@ -5,7 +5,8 @@ only, h = H*s - 2(k//2) + k - 1 (:54-60). Bias is ON unless the `B` tag is given
 
 Nothing new runs on the device: forward is the implicit-GEMM data-gradient kernel of csrc/igemm.hip applied to
 the layer input, the input gradient is F's forward kernel applied to the output gradient, and the filter gradient
-is F's weight-gradient kernel with the roles of activation and gradient swapped."""
+is F's weight-gradient kernel with the roles of activation and gradient swapped. `DC.X` with a filter or stride that differs
+between rows and columns maps onto the per-axis kernels of csrc/conv_rect.hip (ops.conv_rect_*) in exactly the same way."""
 import math
 
 import numpy
@@ -69,13 +70,14 @@ class DeconvLayer(AbstractLayer):
             w = numpy.zeros(shape=fs)
 
         assert fs[1] == self.input_shape[1], "filter channels %i != input channels %i" % (fs[1], self.input_shape[1])
-        assert self.stride[0] == self.stride[1], "only square strides are supported"
-        assert fs[2] == fs[3], "only square filters are supported"
         if self.border_mode != "half":
             raise Exception("Unknown border mode: " + str(self.border_mode))   # deconvolution.py:61
-        self.pad = fs[2] // 2
-        h = self.input_shape[2] * self.stride[0] - 2 * self.pad + fs[2] - 1
-        wd = self.input_shape[3] * self.stride[1] - 2 * self.pad + fs[3] - 1
+        # per axis (deconvolution.py:54-60); a square layer keeps the scalar padding and the square kernels
+        pad2 = (fs[2] // 2, fs[3] // 2)
+        self.anisotropic = fs[2] != fs[3] or self.stride[0] != self.stride[1]
+        self.pad = pad2 if self.anisotropic else pad2[0]
+        h = self.input_shape[2] * self.stride[0] - 2 * pad2[0] + fs[2] - 1
+        wd = self.input_shape[3] * self.stride[1] - 2 * pad2[1] + fs[3] - 1
         self.output_shape = (self.input_shape[0], fs[0], h, wd)
 
         self.cin_p = self.input.cp
@@ -136,8 +138,12 @@ class DeconvLayer(AbstractLayer):
         x = self.input.data
         N = x.shape[0]
         out_shape = (N, self.output_shape[2], self.output_shape[3], self.cout_p)
-        y = ops.conv_dgrad(x, self._w(), out_shape, stride=self.stride[0], pad=self.pad, s_real=self.filter_shape[3],
-                           logical=self._logical())
+        if self.anisotropic:
+            y = ops.conv_rect_dgrad(x, self._w(), out_shape, stride=self.stride, pad=self.pad, s_real=self.filter_shape[3],
+                                    logical=self._logical())
+        else:
+            y = ops.conv_dgrad(x, self._w(), out_shape, stride=self.stride[0], pad=self.pad, s_real=self.filter_shape[3],
+                               logical=self._logical())
         if self.use_bias:
             ops.add_bias(y, self.beta.dev, out=y)
         self.output.data = y
@@ -146,11 +152,14 @@ class DeconvLayer(AbstractLayer):
         dy = self.output.grad
         x = self.input.data
         st, pad, sr = self.stride[0], self.pad, self.filter_shape[3]
+        wgrad, fwd = ops.conv_wgrad, ops.conv_fwd
+        if self.anisotropic:
+            st, wgrad, fwd = self.stride, ops.conv_rect_wgrad, ops.conv_rect_fwd
         if self.omega.grad is not None:
             with ops.wgrad_stream():
-                ops.conv_wgrad(dy, x, self.omega.dev_shape, stride=st, pad=pad, s_real=sr,
-                               out=self.omega.grad.view(self.omega.dev_shape), logical=self._logical())
+                wgrad(dy, x, self.omega.dev_shape, stride=st, pad=pad, s_real=sr,
+                      out=self.omega.grad.view(self.omega.dev_shape), logical=self._logical())
                 if self.use_bias:
                     ops.colsum(dy.view(-1, self.cout_p), out=self.beta.grad)
         if getattr(self.input, "requires_grad", True):
-            self.input.add_grad(ops.conv_fwd(dy, self._w(), stride=st, pad=pad, s_real=sr, logical=self._logical()))
+            self.input.add_grad(fwd(dy, self._w(), stride=st, pad=pad, s_real=sr, logical=self._logical()))

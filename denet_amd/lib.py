@@ -39,6 +39,10 @@ SIGNATURES = {
     "denet_tune_clear": (I, []),
     "denet_conv_fwd_stats": (I, [P, P, P, P, P, P, Z, P] + [I] * 12 + [P]),
     "denet_conv_dgrad": (I, [P, P, P, P] + [I] * 12 + [P]),
+    "denet_conv_rect_fwd": (I, [P] * 5 + [I] * 15 + [P]),
+    "denet_conv_rect_dgrad": (I, [P] * 4 + [I] * 14 + [P]),
+    "denet_conv_rect_wgrad_workspace_bytes": (Z, [I] * 7),
+    "denet_conv_rect_wgrad": (I, [P] * 4 + [Z] + [I] * 14 + [P]),
     "denet_conv_wgrad_workspace_bytes": (Z, [I] * 7),
     "denet_conv_wino_workspace_bytes": (Z, [I] * 6),
     "denet_conv_wino_tune": (I, [P, Z, P, Z] + [I] * 6 + [P]),

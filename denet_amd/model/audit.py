@@ -28,8 +28,13 @@ def conv_layers(model):
 
 
 def layer_geometry(layer):
-    """(fwd geometry tuple of ops.conv_geom, human-readable string) of a ConvLayer on its physical NHWC tensors"""
+    """(fwd geometry tuple of ops.conv_geom, human-readable string) of a ConvLayer on its physical NHWC tensors. An anisotropic
+    layer (filter, stride or padding per axis): the tuple of ops.conv_rect_geom, 14 long; it runs conv_rect_kernel<pass, BM, BN>"""
     n, _, h, w = layer.input_shape
+    if getattr(layer, "anisotropic", False):
+        g = ops.conv_rect_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride, layer.pad, layer.filter_shape[3], layer.ohw)
+        fs = layer.filter_shape
+        return g, "%dx%d %d->%d %dx%d/%dx%d" % (h, w, fs[1], fs[0], fs[2], fs[3], layer.stride[0], layer.stride[1])
     g = ops.conv_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride[0], layer.pad, layer.filter_shape[3], layer.ohw)
     fs = layer.filter_shape
     return g, "%dx%d %d->%d %dx%d/%d" % (h, w, fs[1], fs[0], fs[2], fs[3], layer.stride[0])
@@ -43,6 +48,8 @@ def decisions_cover(model):
     missing = []
     for name, l in conv_layers(model):
         g, txt = layer_geometry(l)
+        if getattr(l, "anisotropic", False):
+            continue                       # one direct kernel, nothing to decide
         three = g[5] == 3 and g[6] == 3 and g[7] == 3 and g[8] == 1 and g[9] == 1 and g[3] >= 32
         if not three:
             continue                       # only the 3x3 stride-1 layers have alternatives

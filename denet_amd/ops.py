@@ -51,6 +51,8 @@ def kernel_symbol(kind, a, b, c):
         return "wino4t_kernel<%d>" % a
     if kind == 17:
         return "dgrad_s2_kernel<%d>" % a
+    if kind == 20:
+        return "conv_rect_kernel<%d, %d, %d>" % (a, b, c)      # pass (0 fwd / 1 dgrad / 2 wgrad), tile BM x BN
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
@@ -1261,6 +1263,74 @@ def conv_wgrad(x, dy, w_shape, stride=1, pad=0, s_real=None, out=None, logical=N
     if PROFILE is not None:
         PROFILE.add(_conv_flops(g, logical))
     direct()
+    return dw
+
+
+# ---- convolution with a per-axis geometry (csrc/conv_rect.hip): `C.X` / `DC.X` layers whose filter, stride or padding differ
+# between rows and columns. One direct kernel per pass, one fixed tile table: no tuned entries, no Winograd, no fused statistics.
+def conv_rect_geom(x_shape, w_shape, stride, pad, s_real=None, ohw=None):
+    """the geometry tuple of the denet_conv_rect_* calls: (N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW). ohw as conv_geom's:
+    an output cut short of the one the padding gives (`same`)"""
+    N, H, W, C = x_shape
+    K, R, S, Cw = w_shape
+    assert Cw == C, (x_shape, w_shape)
+    (sh, sw), (ph, pw) = stride, pad
+    s_real = S if s_real is None else s_real
+    OH = (H + 2 * ph - R) // sh + 1 if sh > 0 else 0
+    OW = (W + 2 * pw - s_real) // sw + 1 if sw > 0 else 0
+    if ohw is not None:
+        assert 0 < ohw[0] <= OH and 0 < ohw[1] <= OW, (ohw, OH, OW)
+        OH, OW = int(ohw[0]), int(ohw[1])
+    return tuple(int(v) for v in (N, H, W, C, K, R, S, s_real, sh, sw, ph, pw, OH, OW))
+
+
+def _conv_rect_flops(g, logical=None):
+    N, H, W, C, K, R, S, s_real, sh, sw, ph, pw, OH, OW = g
+    if logical is not None:
+        C, K = logical
+    return 2.0 * N * OH * OW * K * R * s_real * C
+
+
+def _settled(x):
+    """a pending input (BnLink, UpLink, NchwLink) is written first: the rectangular kernels read plain NHWC tensors"""
+    return x.materialise() if isinstance(x, (BnLink, UpLink, NchwLink)) else x
+
+
+def conv_rect_fwd(x, w, bias=None, add=None, stride=(1, 1), pad=(0, 0), s_real=None, out=None, logical=None, cache=None, relu=False,
+                  ohw=None):
+    x = _settled(x)
+    g = conv_rect_geom(x.shape, w.shape, stride, pad, s_real, ohw)
+    y = out if out is not None else empty(g[0], g[12], g[13], g[4])
+    if cache is not None:
+        cache["bn_stats"] = None               # the batch norm behind measures its own statistics
+    check(_L().denet_conv_rect_fwd(ptr(x), ptr(w), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_rect_fwd")
+    if PROFILE is not None:
+        PROFILE.add(_conv_rect_flops(g, logical))
+    return y
+
+
+def conv_rect_dgrad(dy, w, x_shape, add=None, stride=(1, 1), pad=(0, 0), s_real=None, out=None, logical=None, ohw=None):
+    g = conv_rect_geom(x_shape, w.shape, stride, pad, s_real, ohw)
+    assert tuple(dy.shape) == (g[0], g[12], g[13], g[4]), (dy.shape, g)
+    dx = out if out is not None else empty(*x_shape)
+    check(_L().denet_conv_rect_dgrad(ptr(dy), ptr(w), ptr(add), ptr(dx), *g, stream_ptr()), "conv_rect_dgrad")
+    if PROFILE is not None:
+        PROFILE.add(_conv_rect_flops(g, logical))
+    return dx
+
+
+def conv_rect_wgrad(x, dy, w_shape, stride=(1, 1), pad=(0, 0), s_real=None, out=None, logical=None, ohw=None):
+    x = _settled(x)
+    g = conv_rect_geom(x.shape, w_shape, stride, pad, s_real, ohw)
+    assert tuple(dy.shape) == (g[0], g[12], g[13], g[4]), (dy.shape, g)
+    dw = out if out is not None else empty(*w_shape)
+    N, H, W, C, K, R, S = g[:7]
+    nbytes = int(_L().denet_conv_rect_wgrad_workspace_bytes(N, C, K, R, S, g[12], g[13]))
+    ws = WS.get("wgrad_rect", nbytes) if nbytes else None
+    check(_L().denet_conv_rect_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel() if ws is not None else 0, *g, stream_ptr()),
+          "conv_rect_wgrad")
+    if PROFILE is not None:
+        PROFILE.add(_conv_rect_flops(g, logical))
     return dw
 
 

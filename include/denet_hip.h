@@ -195,6 +195,26 @@ int denet_conv_stem_wgrad_from(const float* x, int x_nchw, const float* dy, floa
 size_t denet_conv_stem_wgrad_workspace_bytes(void);
 int denet_conv_stem_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H, int W,
                           hipStream_t stream);
+/* ---- Convolution with a per-axis geometry (csrc/conv_rect.hip): the `C.X[k, kh, kw, sh, sw]` and `DC.X[...]` tokens (reference:
+ *      denet/layer/convolution.py:99-112, border modes per axis :55-80, conv2d :80-83; deconvolution.py:54-65; gradients:
+ *      tensor.grad, model_cnn.py:318). Filter R x S, stride (sh, sw), zero padding (ph, pw), output OH x OW given by the caller
+ *      (at most the size the padding gives: `same` cuts the last row / column per axis). Tensors and the S / S_real convention
+ *      as denet_conv_fwd; sh and sw are powers of two; the data gradient needs 32 physical channels or more. fp32 on the MFMA
+ *      units, one fixed tile table, nothing measured. A square geometry is valid here as well.
+ *        fwd:   y = conv(x, w) (+ bias[K]) (+ add) (relu != 0: max(., 0))     (convolution.py:80-83, batch_norm_relu.py:34-48)
+ *        dgrad: dx = gradient of x from dy and w (+ add)                      (also the forward pass of DC, deconvolution.py:63-65)
+ *        wgrad: dw [K][R][S][C] from x and dy; taps s >= S_real get 0. The pixel reduction is cut into slices, each written to
+ *               `workspace` (denet_conv_rect_wgrad_workspace_bytes; 0 = no slices, workspace may be NULL) and added in slice
+ *               order: bit-identical from run to run.                                                                       */
+int denet_conv_rect_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N, int H,
+                        int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
+                        hipStream_t stream);
+int denet_conv_rect_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K, int R,
+                          int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW, hipStream_t stream);
+size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int R, int S, int OH, int OW);
+int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H,
+                          int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
+                          hipStream_t stream);
 /* ---- Winograd passes whose input is formed on the fly from the batch-norm layer next to them (csrc/winograd.hip,
  *      wino_prep_kernel). Reference: the BN -> conv chains of the residual blocks (denet/layer/resnet.py:60-90,
  *      batch_norm_relu.py:34-54): a pointwise pass writes a tensor the next convolution's input transform re-reads at once.
