@@ -125,6 +125,10 @@ SIGNATURES = {
     "denet_avgpool_bwd": (I, [P, P] + [I] * 9 + [P]),
     "denet_pool_inv_fwd": (I, [P, P] + [I] * 6 + [P]),
     "denet_pool_inv_bwd": (I, [P, P] + [I] * 6 + [P]),
+    "denet_maxpool_border_fwd": (I, [P, P] + [I] * 10 + [P]),
+    "denet_maxpool_border_bwd": (I, [P, P, P, P] + [I] * 10 + [P]),
+    "denet_avgpool_border_fwd": (I, [P, P] + [I] * 10 + [P]),
+    "denet_avgpool_border_bwd": (I, [P, P] + [I] * 10 + [P]),
     "denet_host_resample_coeffs": (I, [I, D, D, I, I, P, P, L]),
     "denet_image_crop": (I, [P, P] + [I] * 9 + [P]),
     "denet_image_reduce": (I, [P, P, I, I, I, I, P]),

@@ -316,15 +316,17 @@ class ModelCNN:
             if l.type_name == "batchnorm" and getattr(l, "act_behind", None) is not None:
                 l.act_fused = os.environ.get("DENET_BN_ACT_FUSE", "1") != "0" and self._consumers(l.output) == 1
         # a max pool that is the only reader of a BN + ReLU layer's output (the ResNet stem): the two run as one pass in training
+        # (the cuDNN mode only: a border-keeping `P.B` pool clips its windows and sends the gradient to every tie, which the fused
+        # kernels do not do - such a stem runs BN + ReLU, then the pool)
         for a, b in zip(self.layers[:-1], self.layers[1:]):
             a.pool_behind = None
-            if a.type_name == "batchnorm-relu" and b.type_name == "pool" and b.mode == "max" and b.input is a.output \
-                    and self._consumers(a.output) == 1:
+            if a.type_name == "batchnorm-relu" and b.type_name == "pool" and b.mode == "max" and b.ignore_border \
+                    and b.input is a.output and self._consumers(a.output) == 1:
                 a.pool_behind = b
         for a, act, b in zip(self.layers[:-2], self.layers[1:-1], self.layers[2:]):
             # the same for `BN A P` written as three layers: the batch norm writes the fused activation's output
             if a.type_name == "batchnorm" and getattr(a, "act_fused", False) and a.act_behind is act and b.type_name == "pool" \
-                    and b.mode == "max" and b.input is act.output and self._consumers(act.output) == 1:
+                    and b.mode == "max" and b.ignore_border and b.input is act.output and self._consumers(act.output) == 1:
                 a.pool_behind = b
         # a SKIP layer that adds its tap (same channel count: no projection) to the output of the convolution right in front of it
         # (the up-sampling path of the skip models, skip.py:81-86): the addition goes into that convolution's epilogue, and with it the statistics of the batch

@@ -1,5 +1,5 @@
 """Model surgery — the operations of denet/model/modify.py (:37-193) that assemble a DeNet detector from a
-classifier: --class-num, --image-size, --convert-bn-relu (:76-113), --modify-bn (:115-131), --layer-remove
+classifier: --class-num, --image-size, --use-cudnn-pool (:62-68), --convert-bn-relu (:76-113), --modify-bn (:115-131), --layer-remove
 (:153-156), --layer-insert N:DESC (:161-175), --layer-append (:177-184). Like the reference every edit goes
 through the JSON form and a reload, so shapes and wiring are rebuilt from scratch."""
 import copy
@@ -24,6 +24,19 @@ def set_image_size(model, width, height):
     j = model.export_json()
     j["dataShape"] = (3, height, width)
     return _reload(model, j)
+
+
+def use_cudnn_pool(model):
+    """modify.py:62-68: every pool layer with ignore_border false gets pad (1, 1) and ignore_border true, whatever its window is
+    (the published ResNet base models carry one, a 3x3 stride-2 stem pool); a model without such a layer is returned as it is"""
+    j = model.export_json()
+    changed = False
+    for l in j["layers"]:
+        if l["type"] == "pool" and not l["ignoreBorder"]:
+            l["pad"] = (1, 1)
+            l["ignoreBorder"] = True
+            changed = True
+    return _reload(model, j) if changed else model
 
 
 def _bn_to_bnrelu(bn_json):
@@ -182,7 +195,8 @@ def build_parser():
     parser.add_argument("--class-num", type=int, default=None)
     parser.add_argument("--image-size", nargs="+", type=int, default=None)
     parser.add_argument("--use-cudnn-pool", default=False, action="store_true",
-                        help="accepted for the recipes' sake: every pooling layer of this build already pools the cuDNN way")
+                        help="every border-keeping pool layer (ignoreBorder false, `P.B`) becomes a cuDNN-mode one: pad (1, 1), "
+                             "ignoreBorder true")
     parser.add_argument("--convert-bn-relu", default=False, action="store_true")
     parser.add_argument("--merge", default=False, action="store_true", help="merge split layers")
     parser.add_argument("--modify-bn", default=None, nargs="+", type=str, help="enabled momentum eps for batch norm")
@@ -205,7 +219,10 @@ def main(argv=None):
     numpy.random.seed(args.seed)
     model = model_cnn.load_from_file(args.input)
     # the reference edits the loaded object and reloads ONCE (modify.py:153-159); here every edit reloads, so the ones
-    # that drop layers run before the ones that change the input geometry
+    # that drop layers run before the ones that change the input geometry (and --use-cudnn-pool first of all: a border-keeping
+    # pool that the new geometry would refuse is already a cuDNN-mode one by then)
+    if args.use_cudnn_pool:
+        model = use_cudnn_pool(model)
     if args.modify_bn is not None:
         model = modify_bn(model, bool(args.modify_bn[0]), float(args.modify_bn[1]), float(args.modify_bn[2]))
     if args.convert_bn_relu:

@@ -1749,6 +1749,54 @@ def avgpool_bwd(dy, x_shape, k, stride, pad):
     return dx
 
 
+# border-keeping pooling (`P.B` / `P.AB`, csrc/pool_border.hip): windows clipped at the bottom / right edge, no padding
+def pool_border_out(r, k, s):
+    """output size along one axis of pool_2d(..., ignore_border=False) with no padding (Theano's Pool.out_shape as read)"""
+    if s >= k:
+        return (r - 1) // s + 1
+    return max(0, (r - 1 - k + s) // s) + 1
+
+
+def maxpool_border_fwd(x, size, stride):
+    """size = (kh, kw), stride = (sh, sw); the maximum over each clipped window"""
+    N, H, W, C = x.shape
+    OH, OW = pool_border_out(H, size[0], stride[0]), pool_border_out(W, size[1], stride[1])
+    y = empty(N, OH, OW, C)
+    check(_L().denet_maxpool_border_fwd(ptr(x), ptr(y), N, H, W, C, OH, OW, size[0], size[1], stride[0], stride[1], stream_ptr()),
+          "maxpool_border_fwd")
+    return y
+
+
+def maxpool_border_bwd(x, y, dy, size, stride):
+    """every tap equal to its window's maximum receives the window's gradient (no argmax tensor: x == y)"""
+    N, H, W, C = x.shape
+    OH, OW = dy.shape[1], dy.shape[2]
+    assert tuple(y.shape) == tuple(dy.shape) == (N, OH, OW, C), (tuple(x.shape), tuple(y.shape), tuple(dy.shape))
+    dx = torch.empty_like(x)
+    check(_L().denet_maxpool_border_bwd(ptr(x), ptr(y), ptr(dy), ptr(dx), N, H, W, C, OH, OW, size[0], size[1], stride[0],
+                                        stride[1], stream_ptr()), "maxpool_border_bwd")
+    return dx
+
+
+def avgpool_border_fwd(x, size, stride):
+    """the sum over each clipped window divided by the window's own tap count"""
+    N, H, W, C = x.shape
+    OH, OW = pool_border_out(H, size[0], stride[0]), pool_border_out(W, size[1], stride[1])
+    y = empty(N, OH, OW, C)
+    check(_L().denet_avgpool_border_fwd(ptr(x), ptr(y), N, H, W, C, OH, OW, size[0], size[1], stride[0], stride[1], stream_ptr()),
+          "avgpool_border_fwd")
+    return y
+
+
+def avgpool_border_bwd(dy, x_shape, size, stride):
+    N, H, W, C = x_shape
+    assert dy.shape[0] == N and dy.shape[3] == C, (tuple(dy.shape), x_shape)
+    dx = empty(*x_shape)
+    check(_L().denet_avgpool_border_bwd(ptr(dy), ptr(dx), N, H, W, C, dy.shape[1], dy.shape[2], size[0], size[1], stride[0],
+                                        stride[1], stream_ptr()), "avgpool_border_bwd")
+    return dx
+
+
 def pool_inv_fwd(x, fy, fx):
     N, H, W, C = x.shape
     y = empty(N, H * fy, W * fx, C)

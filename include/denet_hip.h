@@ -474,6 +474,20 @@ int denet_avgpool_bwd(const float* dy, float* dx, int N, int H, int W, int C, in
                       int pad, hipStream_t stream);
 int denet_pool_inv_fwd(const float* x, float* y, int N, int H, int W, int C, int fy, int fx, hipStream_t stream);
 int denet_pool_inv_bwd(const float* dy, float* dx, int N, int H, int W, int C, int fy, int fx, hipStream_t stream);
+/* Border-keeping pooling, `P.B` / `P.AB` (denet/layer/pool.py:39-40: pool_2d(..., ignore_border=False), the non-cuDNN path; its
+ * output size is NOT pool.py:32-33 for every geometry). No padding; window (oy, ox) covers rows
+ * oy*sh .. min(oy*sh + kh, H) - 1 and columns ox*sw .. min(ox*sw + kw, W) - 1. NHWC fp32, C % 4 == 0; OH, OW are the caller's
+ * and every window must start inside the map ((OH - 1) * sh < H, (OW - 1) * sw < W). max: the maximum of the clipped window;
+ * its gradient goes to EVERY tap equal to that maximum (x == y; no argmax tensor). avg (average_inc_pad): the sum of the
+ * clipped window over its own tap count; every tap receives dy / count. Both gradients are gathers: deterministic, no atomics. */
+int denet_maxpool_border_fwd(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, int kh, int kw, int sh, int sw,
+                             hipStream_t stream);
+int denet_maxpool_border_bwd(const float* x, const float* y, const float* dy, float* dx, int N, int H, int W, int C, int OH,
+                             int OW, int kh, int kw, int sh, int sw, hipStream_t stream);
+int denet_avgpool_border_fwd(const float* x, float* y, int N, int H, int W, int C, int OH, int OW, int kh, int kw, int sh, int sw,
+                             hipStream_t stream);
+int denet_avgpool_border_bwd(const float* dy, float* dx, int N, int H, int W, int C, int OH, int OW, int kh, int kw, int sh,
+                             int sw, hipStream_t stream);
 
 /* ---- device-side rendering of the data pipeline's augmentation plan (csrc/image.hip)
  *      Replaces the pixel work of denet/dataset/augment.py (add_border :51-61, crop, scale :21-47 = Pillow thumbnail /
