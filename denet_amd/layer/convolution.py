@@ -184,6 +184,10 @@ class ConvLayer(AbstractLayer):
         link = self.input.take_pending_data()
         cache = self._cache()
         cache["train"] = bool(get_train()) and self.enabled and self.omega.grad is not None
+        # an inference pass (never a pass of a training step, frozen layers included) may take the opt-in bf16 kernel
+        # (ops.INFER_PRECISION) unless the layer is kept in fp32 (fp32_only: a softmax reads this layer's output)
+        cache["infer"] = not get_train()
+        cache["fp32_only"] = getattr(self, "fp32_only", False)
         # a batch norm directly behind this layer (it flags its input Act) gets its statistics from this pass's epilogue
         want_stats = bool(get_train()) and getattr(self.output, "want_stats", False)
         cache["bn_final"] = None
@@ -247,6 +251,8 @@ class ConvLayer(AbstractLayer):
         when the weights change), residual `add` and ReLU in the epilogue; writes the batch norm's output"""
         cache = self._cache()
         cache["train"] = False
+        cache["infer"] = True
+        cache["fp32_only"] = getattr(self, "fp32_only", False)
         ent = cache.get("fold")
         if ent is None or ent[0] != ops.WEIGHTS_VERSION or ent[1] is not bn:
             w_f, b_f = ops.bn_fold(self._w(), self.beta.dev if self.use_bias else None, bn.omega.dev, bn.beta.dev,

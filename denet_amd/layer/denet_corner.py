@@ -30,6 +30,7 @@ class DeNetCornerLayer(AbstractLayer):
         self.layers.append(ConvLayer(self.layers, (self.corner_num + self.sample_feat, self.features, 1, 1), (1, 1), True, False))
 
         conv = self.layers[-1]
+        conv.fp32_only = True              # the corner softmax reads it: never the opt-in bf16 kernel (ops.INFER_PRECISION)
         omega = conv.omega.get_value()
         omega[:self.corner_num, :, :, :] = 0.0
         conv.omega.set_value(omega)

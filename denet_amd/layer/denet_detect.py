@@ -52,6 +52,7 @@ class DeNetDetectLayer(AbstractLayer):
         self.s0, self.s1, self.s2 = s0, s1, s2
         self.layers = [ConvLayer([InitialLayer(self.input, self.input_shape)], (s0 + s1 + s2, self.input_shape[1], 1, 1),
                                  (1, 1), True, "valid", 0.0)]
+        self.layers[0].fp32_only = True    # the class softmax reads it: never the opt-in bf16 kernel (ops.INFER_PRECISION)
         if self.use_indfit:
             self.indfit_shape = (self.batch_size, s2, self.sample_num, self.sample_num)
         self.det_shape = (self.batch_size, s0, self.sample_num, self.sample_num)

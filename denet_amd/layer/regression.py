@@ -22,6 +22,8 @@ class RegressionLayer(AbstractLayer):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
+        if isinstance(layers[-1], ConvLayer):
+            layers[-1].fp32_only = True    # the softmax reads it: never the opt-in bf16 kernel (ops.INFER_PRECISION)
         if use_center:
             valid = [(0, self.input_shape[-2] // 2, self.input_shape[-1] // 2)]
         self.valid = [tuple(int(a) for a in v) for v in json_param.get("valid", valid)]     # (JSON gives lists)

@@ -142,6 +142,11 @@ def build_parser():
     parser.add_argument("--params", default="", type=str, help="Additional detection params")
     parser.add_argument("--device-render", default=False, action="store_true",
                         help="detect mode: scale / crop the images on the GPU instead of in the loader processes")
+    from .. import ops
+    parser.add_argument("--precision", default=ops.INFER_PRECISION, choices=ops.PRECISIONS,
+                        help="arithmetic of the inference convolutions, every predict mode: fp32 (the default, exact) or bf16 (opt-in: "
+                             "operands rounded to bf16 on the bf16 matrix cores, fp32 accumulation; outside the 1e-3 parity budget, "
+                             "RoI lists and detections may differ from fp32)")
     return parser
 
 
@@ -151,16 +156,18 @@ def main(argv=None):
     logging.init(args)
     model = model_cnn.load_from_file(args.model, args.batch_size)
     data = dataset.load(args.input, args.extension, class_labels=model.class_labels, thread_num=args.thread_num)
-    if "single" in args.predict_mode:
-        test_single(args.predict_mode, model, data)
-    elif "multicrop" in args.predict_mode:
-        assert "multicrop" in args.extension
-        test_multicrop(args.predict_mode, model, data)
-    elif "detect" in args.predict_mode:
-        test_detector(args.predict_mode, model, data, args.results, args.params, device_render=args.device_render,
-                      thread_num=args.thread_num)
-    else:
-        raise NotImplementedError("predict mode '%s' (segmentation is outside the detection hot path)" % args.predict_mode)
+    from .. import ops
+    with ops.infer_precision(args.precision):
+        if "single" in args.predict_mode:
+            test_single(args.predict_mode, model, data)
+        elif "multicrop" in args.predict_mode:
+            assert "multicrop" in args.extension
+            test_multicrop(args.predict_mode, model, data)
+        elif "detect" in args.predict_mode:
+            test_detector(args.predict_mode, model, data, args.results, args.params, device_render=args.device_render,
+                          thread_num=args.thread_num)
+        else:
+            raise NotImplementedError("predict mode '%s' (segmentation is outside the detection hot path)" % args.predict_mode)
     return 0
 
 

@@ -75,7 +75,8 @@ def update_bn(model, batches, log=None, device_budget=DEVICE_BUDGET):
         batches = [b.cuda().float().contiguous() if isinstance(b, torch.Tensor)
                    else torch.from_numpy(numpy.ascontiguousarray(b, dtype=numpy.float32)).cuda() for b in batches]
     out = []
-    with ops.infer_fold(False):
+    # (the statistics are those of the exact fp32 passes whatever ops.INFER_PRECISION / DENET_INFER_BF16 say)
+    with ops.infer_fold(False), ops.infer_precision("fp32"):
         for i, (layer, top) in enumerate(chosen):
             log("Estimating mean and var for layer %i with %i batches" % (i, n))
             shape = layer.input_shape

@@ -53,6 +53,8 @@ def kernel_symbol(kind, a, b, c):
         return "dgrad_s2_kernel<%d>" % a
     if kind == 20:
         return "conv_rect_kernel<%d, %d, %d>" % (a, b, c)      # pass (0 fwd / 1 dgrad / 2 wgrad), tile BM x BN
+    if kind == 21:
+        return "conv_bf16_kernel<%d, %d>" % (a, b)             # tile BM x BN of the opt-in bf16 inference kernel
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
@@ -581,6 +583,18 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
     cache["bn_stats"] = (partial sums tensor, rows) for bn_fwd_train(pre=...), or None when the chosen kernel cannot.
     link (BnLink, x = None): the input is the output of a batch norm whose pointwise pass has not run; a Winograd pass evaluates
     it inside its input transform, every other implementation materialises it first. link.result is the activation afterwards."""
+    if INFER_PRECISION != "fp32" and cache is not None and cache.get("infer") and not cache.get("train") and not bn_stats \
+            and not cache.get("fp32_only") and _check_precision(INFER_PRECISION) == "bf16":
+        # OPT-IN bf16 inference (csrc/conv_bf16.hip): an inference pass of a layer that is not kept in fp32 (ConvLayer.fp32_only);
+        # a geometry the kernel does not take (fewer than 32 channels) falls through to the fp32 kernels
+        xs = link.x.shape if link is not None else (up.shape if up is not None else x.shape)
+        g = conv_geom(xs, w.shape, stride, pad, s_real, ohw)
+        if g[3] % 32 == 0 and g[5] == g[6] == g[7]:
+            if link is not None:
+                x = link.materialise()
+            if up is not None:
+                x = up.materialise()
+            return _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu)
     if link is not None:
         g = conv_geom(link.x.shape, w.shape, stride, pad, s_real, ohw)
         tile = _decided(0, g)
@@ -1580,6 +1594,62 @@ def infer_fold(enabled):
         yield
     finally:
         INFER_FOLD = was
+
+
+# OPT-IN, never the headline (bench.py never sets it): inference convolutions with both operands rounded to bf16 on the bf16
+# matrix cores (csrc/conv_bf16.hip; the numerics contract is in DESIGN.md, "bf16 inference"). "fp32" or "bf16"; all or nothing,
+# no per-layer mixing beyond the layers that always stay fp32 (the stem, anisotropic and DC layers, convolutions a softmax reads)
+PRECISIONS = ("fp32", "bf16")
+INFER_PRECISION = "bf16" if os.environ.get("DENET_INFER_BF16", "0") not in ("0", "") else "fp32"
+
+
+def _check_precision(name):
+    if name not in PRECISIONS:
+        raise ValueError("inference precision %r: expected one of %s" % (name, ", ".join(PRECISIONS)))
+    return name
+
+
+@contextlib.contextmanager
+def infer_precision(name):
+    """INFER_PRECISION set to `name` ("fp32" / "bf16", anything else raises ValueError) inside the block, restored on the way
+    out. Only inference passes read it: training and model-update-bn (which forces "fp32") never take the bf16 kernel"""
+    global INFER_PRECISION
+    _check_precision(name)
+    was = INFER_PRECISION
+    INFER_PRECISION = name
+    try:
+        yield
+    finally:
+        INFER_PRECISION = was
+
+
+def filter_to_bf16(w):
+    """bf16 copy (round to nearest-even) of an fp32 filter, same layout"""
+    w16 = torch.empty(w.shape, dtype=torch.bfloat16, device="cuda")
+    check(_L().denet_filter_to_bf16(ptr(w), ptr(w16), w.numel(), stream_ptr()), "filter_to_bf16")
+    return w16
+
+
+def conv_fwd_bf16(x, w16, bias=None, add=None, stride=1, pad=0, out=None, relu=False, ohw=None):
+    """y = epilogue(conv(bf16(x), w16)) accumulated in fp32: x fp32 NHWC (rounded when staged), w16 = filter_to_bf16(filter)"""
+    g = conv_geom(x.shape, w16.shape, stride, pad, None, ohw)
+    y = out if out is not None else empty(g[0], g[10], g[11], g[4])
+    check(_L().denet_conv_fwd_bf16(ptr(x), ptr(w16), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_fwd_bf16")
+    return y
+
+
+def _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu):
+    """conv_fwd's bf16 inference branch: the bf16 filter is made once per weights version and per filter tensor (the folded one
+    of ConvLayer.forward_folded or the layer's own), kept in the layer's cache like cache["fold"] / cache["u_test"]"""
+    ent = cache.get("w16")
+    if ent is None or ent[0] != WEIGHTS_VERSION or ent[1] != w.data_ptr() or ent[2].shape != w.shape:
+        ent = cache["w16"] = (WEIGHTS_VERSION, w.data_ptr(), filter_to_bf16(w), w)      # (w is held: its address stays its own)
+    N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
+    y = out if out is not None else empty(N, OH, OW, K)
+    check(_L().denet_conv_fwd_bf16(ptr(x), ptr(ent[2]), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_fwd_bf16")
+    if PROFILE is not None:
+        PROFILE.add(_conv_flops(g, logical))
+    return y
 
 
 def bn_moments_workspace(M, C):

@@ -215,6 +215,16 @@ size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int R, int S, 
 int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H,
                           int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
                           hipStream_t stream);
+/* ---- OPT-IN bf16 inference (csrc/conv_bf16.hip), never the fp32 path and never taken by training: the forward pass of a square
+ *      convolution (geometry and tensors as denet_conv_fwd_act; C % 32 = 0, every tap real) with both operands rounded to bf16,
+ *          y = epilogue( sum over taps and channels of bf16(x) * bf16(w) ),  accumulated in fp32 (v_mfma_f32_32x32x16_bf16).
+ *      x stays fp32 in memory and is rounded to nearest-even when it is staged; w16 is the [K][R][S][C] filter as bf16, made
+ *      from the fp32 one (n elements, round to nearest-even) by denet_filter_to_bf16. bias, add and ReLU are applied in fp32 in
+ *      the order of the fp32 epilogue; y is fp32. 128-pixel tiles against 128 / 64 / 32 filters by K alone; the accumulation
+ *      order is fixed: bit-identical from run to run.                                                                         */
+int denet_filter_to_bf16(const float* w, void* w16, long n, hipStream_t stream);
+int denet_conv_fwd_bf16(const float* x, const void* w16, const float* bias, const float* add, float* y, int relu, int N, int H,
+                        int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream);
 /* ---- Winograd passes whose input is formed on the fly from the batch-norm layer next to them (csrc/winograd.hip,
  *      wino_prep_kernel). Reference: the BN -> conv chains of the residual blocks (denet/layer/resnet.py:60-90,
  *      batch_norm_relu.py:34-54): a pointwise pass writes a tensor the next convolution's input transform re-reads at once.
