@@ -188,8 +188,14 @@ class ConvLayer(AbstractLayer):
         # (ops.INFER_PRECISION) unless the layer is kept in fp32 (fp32_only: a softmax reads this layer's output)
         cache["infer"] = not get_train()
         cache["fp32_only"] = getattr(self, "fp32_only", False)
-        # a batch norm directly behind this layer (it flags its input Act) gets its statistics from this pass's epilogue
-        want_stats = bool(get_train()) and getattr(self.output, "want_stats", False)
+        # a training-mode pass of an eligible layer takes the opt-in bf16 kernels (ops.TRAIN_PRECISION); the mode is recorded here,
+        # and the backward pass of this step follows the record whatever the global says by then
+        bf16 = cache["bf16_train"] = bool(get_train()) and ops.train_bf16() and self._bf16_train_eligible()
+        if bf16 and ops.HEAD_BF16X3:
+            raise ValueError(ops.BF16_CONFLICT)   # (also for a model whose build_train_func ran before the mode was switched on)
+        # a batch norm directly behind this layer (it flags its input Act) gets its statistics from this pass's epilogue (never the
+        # bf16 kernel's: the batch norm then measures its own, as behind an anisotropic layer)
+        want_stats = bool(get_train()) and getattr(self.output, "want_stats", False) and not bf16
         cache["bn_final"] = None
         self._planar_x = None
         if isinstance(link, ops.NchwLink):
@@ -211,7 +217,7 @@ class ConvLayer(AbstractLayer):
         if skip is not None and add is None and get_train() and ctx is not None:
             # the SKIP layer behind adds its tap to this layer's output: here, in the epilogue (ModelCNN.build_train_func links the
             # two); the sum is the SKIP layer's output, and what a batch norm behind THAT wants to know about it is measured here
-            want_skip_stats = getattr(skip.output, "want_stats", False)
+            want_skip_stats = getattr(skip.output, "want_stats", False) and not bf16
             sbn = getattr(skip.output, "stats_bn", None) if want_skip_stats else None
             cache["bn_final"] = sbn.stats_final(skip.output) if sbn is not None else None
             y = ops.conv_fwd(x, self._w(), bias=None, add=skip.y.data, stride=self.stride[0], pad=self.pad,
@@ -236,6 +242,15 @@ class ConvLayer(AbstractLayer):
         self._settle_up(up)
         self.output.stats = cache.pop("bn_stats", None) if want_stats else None
 
+    def _bf16_train_eligible(self):
+        """the layers ops.TRAIN_PRECISION = "bf16" moves ("bf16 training"): square, not anisotropic, 32 physical input
+        channels or more (never the stem), every tap real, a stride that is a power of two (the bf16 kernels take no other), no cut
+        output, not kept in fp32 (a softmax reads the output)"""
+        fs = self.filter_shape
+        st = self.stride[0]
+        return (type(self) is ConvLayer and not self.anisotropic and fs[2] == fs[3] and self.cp % 32 == 0 and self.s_pad == fs[3]
+                and st > 0 and st & (st - 1) == 0 and self.ohw is None and not getattr(self, "fp32_only", False))
+
     def _settle_up(self, up):
         """after a forward pass on an un-written up-sampled input: the tensor if the pass had to make it, else still pending (the
         filter gradient asks for it on its own stream, anybody else through Act.data)"""
@@ -253,6 +268,7 @@ class ConvLayer(AbstractLayer):
         cache["train"] = False
         cache["infer"] = True
         cache["fp32_only"] = getattr(self, "fp32_only", False)
+        cache["bf16_train"] = False            # (what a training step recorded is that step's: inference never reads TRAIN_PRECISION)
         ent = cache.get("fold")
         if ent is None or ent[0] != ops.WEIGHTS_VERSION or ent[1] is not bn:
             w_f, b_f = ops.bn_fold(self._w(), self.beta.dev if self.use_bias else None, bn.omega.dev, bn.beta.dev,
@@ -312,7 +328,8 @@ class ConvLayer(AbstractLayer):
         # gradient of that output, and a Winograd pass can leave that batch norm's two backward reductions behind (ops.BnSums)
         sums = None
         bn = self.input.bn_producer
-        if (ops.BWD_SUMS and bn is not None and self._cache().get("train") and getattr(self.input, "requires_grad", True)
+        bf16 = bool(self._cache().get("bf16_train"))      # (bf16 mode: that batch norm does its own reductions)
+        if (ops.BWD_SUMS and bn is not None and not bf16 and self._cache().get("train") and getattr(self.input, "requires_grad", True)
                 and not getattr(self, "not_last_writer", False)):
             sums = bn.sums_request(self.input)
         link = self.output.take_pending_grad()
@@ -321,7 +338,7 @@ class ConvLayer(AbstractLayer):
             # data- and filter-gradient passes are Winograd passes forms it inside ONE transform kernel that feeds both
             fs = self.filter_shape
             if (self.enabled and self.omega.grad is not None and getattr(self.input, "requires_grad", True) and not self.use_bias
-                    and fs[2] == 3 and fs[3] == 3 and st == 1 and self.stride[1] == 1 and pad == 1 and self.ohw is None):
+                    and not bf16 and fs[2] == 3 and fs[3] == 3 and st == 1 and self.stride[1] == 1 and pad == 1 and self.ohw is None):
                 dx = ops.conv_backward_linked(link, x, self._w(), self.omega.dev_shape, self.input.grad,
                                               self.omega.grad.view(self.omega.dev_shape), self._cache(), stride=st, pad=pad,
                                               s_real=sr, logical=self._logical(), sums=sums)

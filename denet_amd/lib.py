@@ -45,6 +45,11 @@ SIGNATURES = {
     "denet_conv_rect_wgrad": (I, [P] * 4 + [Z] + [I] * 14 + [P]),
     "denet_filter_to_bf16": (I, [P, P, L, P]),
     "denet_conv_fwd_bf16": (I, [P] * 5 + [I] * 13 + [P]),
+    "denet_filter_to_bf16_dgrad": (I, [P, P, I, I, I, I, P]),
+    "denet_conv_dgrad_bf16": (I, [P] * 4 + [I] * 12 + [P]),
+    "denet_conv_wgrad_bf16_slices": (I, [I] * 7),
+    "denet_conv_wgrad_bf16_workspace_bytes": (Z, [I] * 7),
+    "denet_conv_wgrad_bf16": (I, [P] * 4 + [Z] + [I] * 12 + [P]),
     "denet_conv_wgrad_workspace_bytes": (Z, [I] * 7),
     "denet_conv_wino_workspace_bytes": (Z, [I] * 6),
     "denet_conv_wino_tune": (I, [P, Z, P, Z] + [I] * 6 + [P]),

@@ -291,6 +291,9 @@ class ModelCNN:
         if use_acc_mode and solver_mode == "adam":
             raise NotImplementedError("--use-acc-mode averages would-be updates; that equals one update with the mean "
                                       "gradient only for the linear solvers (sgd, torch, nesterov)")
+        from .. import ops as _ops
+        if _ops.train_bf16() and _ops.HEAD_BF16X3:
+            raise ValueError(_ops.BF16_CONFLICT)
         self.use_acc_mode = bool(use_acc_mode)
         self._acc = None
         self.solver_mode = solver_mode

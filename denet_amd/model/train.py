@@ -122,6 +122,11 @@ def build_parser(single=True):
         parser.add_argument("--skip-train", default=False, action="store_true",
                             help="Skip training of model (epochs still anneal, test and save)")
     parser.add_argument("--skip-layer-updates", type=int, nargs="+", default=[])
+    from .. import ops
+    parser.add_argument("--precision", default=ops.TRAIN_PRECISION, choices=ops.PRECISIONS,
+                        help="arithmetic of the training convolutions: fp32 (the default, exact) or bf16 (opt-in: the eligible layers' "
+                             "three passes with operands rounded to bf16 on the bf16 matrix cores, fp32 accumulation, fp32 master "
+                             "weights and solver; outside the 1e-3 parity budget, DESIGN.md)")
     parser.add_argument("--model-desc", default=["C[100,7]", "P[2]", "C[150,4]", "P[2]", "C[250,4]", "P[2]", "C[300,1]", "R"],
                         nargs="+", type=str)
     return parser
@@ -212,7 +217,9 @@ def main(argv=None):
     test_data = None
     if args.test:
         test_data = load_dataset(args.test, args.seed, args.extension, False, args.thread_num, train_data.class_labels)
-    train(args, train_data, test_data=test_data)
+    from .. import ops
+    with ops.train_precision(args.precision):
+        train(args, train_data, test_data=test_data)
     return 0
 
 

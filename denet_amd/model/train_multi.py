@@ -179,7 +179,9 @@ def main(argv=None):
     data = train_mod.load_dataset(args.train, args.seed, args.extension, True, args.thread_num)
     if not hasattr(data, "images"):
         raise SystemExit("model-train-multi shards the image list of an MSCOCO / Pascal VOC / ImageNet dataset")
-    train(args, data, dp)
+    from .. import ops
+    with ops.train_precision(args.precision):
+        train(args, data, dp)
     if hasattr(data, "image_loader"):
         data.image_loader.close()
     if dp is not None:

@@ -54,8 +54,11 @@ def kernel_symbol(kind, a, b, c):
     if kind == 20:
         return "conv_rect_kernel<%d, %d, %d>" % (a, b, c)      # pass (0 fwd / 1 dgrad / 2 wgrad), tile BM x BN
     if kind == 21:
-        return "conv_bf16_kernel<%d, %d>" % (a, b)             # tile BM x BN of the opt-in bf16 inference kernel
-    fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel"}.get(kind)
+        return "conv_bf16_kernel<%d, %d>" % (a, b)             # tile BM x BN of the opt-in bf16 kernel (forward, data gradient)
+    if kind == 22:
+        return "conv_bf16_wgrad_kernel<%d, %d>" % (a, b)       # tile BM x BN of the opt-in bf16 filter gradient
+    fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
+             24: "filter_to_bf16_dgrad_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
 
@@ -595,6 +598,20 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
             if up is not None:
                 x = up.materialise()
             return _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu)
+    if cache is not None and cache.get("bf16_train") and not cache.get("infer"):
+        # OPT-IN bf16 training (ConvLayer.forward recorded the mode for this step; never an inference pass, whatever an earlier
+        # training step left in the layer's cache): the bf16 kernel on the raw filter, a pending
+        # input written first, no statistics in the epilogue - the batch norm behind measures its own
+        assert not bn_stats and not relu
+        if link is not None:
+            x = link.materialise()
+        if up is not None:
+            x = up.materialise()
+        g = conv_geom(x.shape, w.shape, stride, pad, s_real, ohw)
+        cache["bn_stats"] = None
+        _note_fwd_tile(cache, 0)
+        cache["fwd_tile_train"] = 0            # (no Winograd filters for wino_prefetch_filters to prepare, trained or frozen)
+        return _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, False, key="w16_train")
     if link is not None:
         g = conv_geom(link.x.shape, w.shape, stride, pad, s_real, ohw)
         tile = _decided(0, g)
@@ -1137,6 +1154,20 @@ def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None,
     g = conv_geom(x_shape, w.shape, stride, pad, s_real, ohw)
     assert tuple(dy.shape) == (g[0], g[10], g[11], g[4]), (dy.shape, g)
     dx = out if out is not None else empty(*x_shape)
+    if cache is not None and cache.get("bf16_train") and conv_dgrad_bf16_ok(g):
+        # OPT-IN bf16 training: the forward kernel on dy over the rotated, transposed bf16 filter (made once per weights version);
+        # no backward sums - the batch norm in front does its own reductions. A strided layer falls through to the fp32 kernels
+        assert sums is None
+        ent = cache.get("w16_dgrad")
+        if ent is None or ent[0] != WEIGHTS_VERSION or ent[1] != w.data_ptr() or ent[2].shape != (g[3], g[5], g[6], g[4]):
+            ent = cache["w16_dgrad"] = (WEIGHTS_VERSION, w.data_ptr(), filter_to_bf16_dgrad(w), w)
+        cache["dgrad_tile"] = 0
+        for k in ("dgrad_1x1t", "dgrad_t", "dgrad_s2"):      # (nothing for wino_prefetch_filters to prepare for this layer)
+            cache.pop(k, None)
+        check(_L().denet_conv_dgrad_bf16(ptr(dy), ptr(ent[2]), ptr(add), ptr(dx), *g, stream_ptr()), "conv_dgrad_bf16")
+        if PROFILE is not None:
+            PROFILE.add(_conv_flops(g, logical))
+        return dx
     if add is None and _bf16x3_geom(g):
         N, H, W, C, K = g[0], g[1], g[2], g[3], g[4]
         if cache is not None:
@@ -1255,6 +1286,10 @@ def conv_wgrad(x, dy, w_shape, stride=1, pad=0, s_real=None, out=None, logical=N
     g = conv_geom(x.shape, w_shape, stride, pad, s_real, ohw)
     assert tuple(dy.shape) == (g[0], g[10], g[11], g[4]), (dy.shape, g)
     dw = out if out is not None else empty(*w_shape)
+    if cache is not None and cache.get("bf16_train"):
+        # OPT-IN bf16 training: the bf16 filter gradient (csrc/conv_bf16_train.hip), every stride
+        cache["V_tile"] = None
+        return conv_wgrad_bf16(x, dy, w_shape, stride=stride, pad=pad, out=dw, ohw=ohw, logical=logical)
     if _bf16x3_geom(g):
         N, H, W, C, K = g[0], g[1], g[2], g[3], g[4]
         M = N * H * W                                                                   # dw[k][c] = sum over pixels dy^T[k][pix] x^T[c][pix]
@@ -1638,18 +1673,100 @@ def conv_fwd_bf16(x, w16, bias=None, add=None, stride=1, pad=0, out=None, relu=F
     return y
 
 
-def _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu):
-    """conv_fwd's bf16 inference branch: the bf16 filter is made once per weights version and per filter tensor (the folded one
-    of ConvLayer.forward_folded or the layer's own), kept in the layer's cache like cache["fold"] / cache["u_test"]"""
-    ent = cache.get("w16")
+def _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu, key="w16"):
+    """conv_fwd's bf16 branches: the bf16 filter is made once per weights version and per filter tensor (inference, key "w16": the
+    folded one of ConvLayer.forward_folded or the layer's own; training, key "w16_train": the raw one), kept in the layer's cache
+    like cache["fold"] / cache["u_test"]"""
+    ent = cache.get(key)
     if ent is None or ent[0] != WEIGHTS_VERSION or ent[1] != w.data_ptr() or ent[2].shape != w.shape:
-        ent = cache["w16"] = (WEIGHTS_VERSION, w.data_ptr(), filter_to_bf16(w), w)      # (w is held: its address stays its own)
+        ent = cache[key] = (WEIGHTS_VERSION, w.data_ptr(), filter_to_bf16(w), w)        # (w is held: its address stays its own)
     N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
     y = out if out is not None else empty(N, OH, OW, K)
     check(_L().denet_conv_fwd_bf16(ptr(x), ptr(ent[2]), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_fwd_bf16")
     if PROFILE is not None:
         PROFILE.add(_conv_flops(g, logical))
     return y
+
+
+# OPT-IN, never the headline (bench.py never sets it): the eligible convolutions of a TRAINING step with both operands rounded to
+# bf16 on the bf16 matrix cores, fp32 accumulation, fp32 master weights and solver (csrc/conv_bf16.hip, csrc/conv_bf16_train.hip; the
+# numerics contract is in DESIGN.md, "bf16 training"). Independent of INFER_PRECISION. ConvLayer.forward reads it and records it in
+# the layer's cache (cache["bf16_train"]); the backward pass of that step follows the recorded value
+TRAIN_PRECISION = "bf16" if os.environ.get("DENET_TRAIN_BF16", "0") not in ("0", "") else "fp32"
+BF16_CONFLICT = ("bf16 training (ops.TRAIN_PRECISION / DENET_TRAIN_BF16) and DENET_HEAD_BF16X3 are two different roundings of the "
+                 "same layers: choose one")
+
+
+@contextlib.contextmanager
+def train_precision(name):
+    """TRAIN_PRECISION set to `name` ("fp32" / "bf16", anything else raises ValueError) inside the block, restored on the way out.
+    Only training-mode passes read it"""
+    global TRAIN_PRECISION
+    if name not in PRECISIONS:
+        raise ValueError("training precision %r: expected one of %s" % (name, ", ".join(PRECISIONS)))
+    was = TRAIN_PRECISION
+    TRAIN_PRECISION = name
+    try:
+        yield
+    finally:
+        TRAIN_PRECISION = was
+
+
+def train_bf16():
+    """True while training-mode passes take the bf16 kernels; a value that is neither name raises where it is read"""
+    if TRAIN_PRECISION not in PRECISIONS:
+        raise ValueError("training precision %r: expected one of %s" % (TRAIN_PRECISION, ", ".join(PRECISIONS)))
+    return TRAIN_PRECISION == "bf16"
+
+
+def filter_to_bf16_dgrad(w):
+    """the data gradient's filter: wt[c][R-1-r][S-1-s][k] = bf16(w[k][r][s][c]), rounded once from the fp32 filter"""
+    K, R, S, C = w.shape
+    wt = torch.empty((C, R, S, K), dtype=torch.bfloat16, device="cuda")
+    check(_L().denet_filter_to_bf16_dgrad(ptr(w), ptr(wt), K, R, S, C, stream_ptr()), "filter_to_bf16_dgrad")
+    if PROFILE is not None:
+        PROFILE.add(0.0)
+    return wt
+
+
+def conv_dgrad_bf16_ok(g):
+    """the geometries the bf16 data gradient takes: stride 1, pad <= R - 1, an uncut output (anything else runs the fp32 kernels)"""
+    N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
+    return stride == 1 and pad <= R - 1 and R == S == s_real and C % 32 == 0 and K % 32 == 0 \
+        and OH == H + 2 * pad - R + 1 and OW == W + 2 * pad - S + 1
+
+
+def conv_dgrad_bf16(dy, wt16, x_shape, add=None, pad=0, out=None):
+    """dx = sum bf16(dy) * wt16 (+ add), accumulated in fp32: dy fp32 NHWC (rounded when staged), wt16 = filter_to_bf16_dgrad(w)"""
+    C, R, S, K = wt16.shape
+    g = conv_geom(x_shape, (K, R, S, C), 1, pad, None)
+    assert tuple(dy.shape) == (g[0], g[10], g[11], g[4]), (dy.shape, g)
+    dx = out if out is not None else empty(*x_shape)
+    check(_L().denet_conv_dgrad_bf16(ptr(dy), ptr(wt16), ptr(add), ptr(dx), *g, stream_ptr()), "conv_dgrad_bf16")
+    return dx
+
+
+def conv_wgrad_bf16_slices(g):
+    """slices of the pixel reduction of the bf16 filter gradient of geometry g (ops.conv_geom)"""
+    N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
+    return int(_L().denet_conv_wgrad_bf16_slices(N, C, K, R, S, OH, OW))
+
+
+def conv_wgrad_bf16(x, dy, w_shape, stride=1, pad=0, out=None, ohw=None, logical=None):
+    """dw = sum over pixels bf16(dy) * bf16(x), accumulated in fp32 (slices added in slice order): x, dy fp32 NHWC"""
+    g = conv_geom(x.shape, w_shape, stride, pad, None, ohw)
+    assert tuple(dy.shape) == (g[0], g[10], g[11], g[4]), (dy.shape, g)
+    dw = out if out is not None else empty(*w_shape)
+    N, H, W, C, K, R, S = g[:7]
+    nbytes = int(_L().denet_conv_wgrad_bf16_workspace_bytes(N, C, K, R, S, g[10], g[11]))
+    ws = WS.get("wgrad_bf16", nbytes) if nbytes else None
+    check(_L().denet_conv_wgrad_bf16(ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel() if ws is not None else 0, *g, stream_ptr()),
+          "conv_wgrad_bf16")
+    if PROFILE is not None:
+        PROFILE.add(_conv_flops(g, logical))
+        if nbytes:
+            PROFILE.add(0.0)               # (the reduce kernel's record)
+    return dw
 
 
 def bn_moments_workspace(M, C):

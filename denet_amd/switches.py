@@ -42,6 +42,7 @@ SWITCHES = {
     "DENET_UP_LINK": ("1", "kernels", "the pool-inverse layer read inside the next convolution's input transform"),
     "DENET_INFER_FOLD": ("1", "kernels", "inference: batch norm folded into the convolution in front of it"),
     "DENET_INFER_BF16": ("0", "kernels", "OPT-IN, never the headline: inference convolutions with bf16 operands on the bf16 matrix cores (ops.INFER_PRECISION = \"bf16\", model-predict --precision bf16); training and model-update-bn stay fp32"),
+    "DENET_TRAIN_BF16": ("0", "kernels", "OPT-IN, never the headline: the eligible training convolutions (forward, data gradient at stride 1, filter gradient) with bf16 operands on the bf16 matrix cores, fp32 accumulation and solver (ops.TRAIN_PRECISION = \"bf16\", model-train --precision bf16); inference and bench.py are untouched"),
     # ---- streams, RoI path ---------------------------------------------------------------------------------------------
     "DENET_WGRAD_STREAM": ("1", "kernels", "the filter-gradient chain of the backward sweep on a second stream"),
     "DENET_SHORT_HANDOFF": ("1", "host", "the short forms of the RoI hand-off (device-side editing / one native call)"),

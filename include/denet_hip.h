@@ -225,6 +225,24 @@ int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw, float* wor
 int denet_filter_to_bf16(const float* w, void* w16, long n, hipStream_t stream);
 int denet_conv_fwd_bf16(const float* x, const void* w16, const float* bias, const float* add, float* y, int relu, int N, int H,
                         int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream);
+/* ---- OPT-IN bf16 training (csrc/conv_bf16_train.hip), never the fp32 path: the backward passes of a square convolution with both
+ *      operands rounded to bf16 (nearest-even, where they are staged), fp32 accumulation on v_mfma_f32_32x32x16_bf16; the forward
+ *      pass of the mode is denet_conv_fwd_bf16 on the raw filter. Geometry and tensors as denet_conv_dgrad / denet_conv_wgrad
+ *      (the FORWARD geometry; C % 32 = 0, K % 32 = 0, every tap real); all tensors fp32 in memory.
+ *        denet_filter_to_bf16_dgrad: wt16[c][R-1-r][S-1-s][k] = bf16(w[k][r][s][c]), the filter of the data gradient.
+ *        denet_conv_dgrad_bf16:      dx = sum bf16(dy) * wt16 (+ add): the forward kernel on dy with padding R-1-pad. stride 1,
+ *                                    pad <= R-1 and an uncut output only; anything else is an error (the caller runs fp32).
+ *        denet_conv_wgrad_bf16:      dw[K][R][S][C] = sum over pixels bf16(dy) * bf16(x), stride 1 or 2. The pixel reduction is cut
+ *                                    into denet_conv_wgrad_bf16_slices slices (geometry only, at most 128), each written to
+ *                                    `workspace` (denet_conv_wgrad_bf16_workspace_bytes; 0 = one slice, workspace may be NULL) and
+ *                                    added in slice order: bit-identical from run to run.                                        */
+int denet_filter_to_bf16_dgrad(const float* w, void* wt16, int K, int R, int S, int C, hipStream_t stream);
+int denet_conv_dgrad_bf16(const float* dy, const void* wt16, const float* add, float* dx, int N, int H, int W, int C, int K, int R,
+                          int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream);
+int denet_conv_wgrad_bf16_slices(int N, int C, int K, int R, int S, int OH, int OW);
+size_t denet_conv_wgrad_bf16_workspace_bytes(int N, int C, int K, int R, int S, int OH, int OW);
+int denet_conv_wgrad_bf16(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H, int W,
+                          int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream);
 /* ---- Winograd passes whose input is formed on the fly from the batch-norm layer next to them (csrc/winograd.hip,
  *      wino_prep_kernel). Reference: the BN -> conv chains of the residual blocks (denet/layer/resnet.py:60-90,
  *      batch_norm_relu.py:34-54): a pointwise pass writes a tensor the next convolution's input transform re-reads at once.
