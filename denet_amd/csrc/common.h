@@ -64,6 +64,14 @@ struct FastDiv {
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
+// log2(v) when v is a power of two, else -1
+static inline int ilog2_exact(int v) {
+    if (v <= 0) return -1;
+    int s = 0;
+    while ((1 << s) < v) s++;
+    return ((1 << s) == v) ? s : -1;
+}
+
 // XCD-aware bijective remap of a linear workgroup id: workgroup b runs on XCD b%8; give each
 // XCD a contiguous chunk of the tile space so neighbouring tiles share one L2.
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t b, uint32_t nwg) {

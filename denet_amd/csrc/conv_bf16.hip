@@ -14,20 +14,12 @@
 //                 cover all 64 banks, gemm3b.hip). The next chunk travels global -> VGPR while the current one is multiplied;
 //                 it is converted and written to the other buffer behind the products; one barrier per chunk.
 // Order:          every output element is one fixed chain chunk by chunk, 2 MFMA k-steps per chunk: bit-identical run to run.
-#include "common.h"
+#include "bf16_mma.h"
 #include "../../include/denet_hip.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BK = 32;
-constexpr int ROWB = 80;                              // bytes per LDS row: 32 bf16 + 16 bytes of padding
-constexpr int OOBV = (int)0xF0000000u;                // beyond every extent check_bf16 admits: the lane reads 0
 
 struct Bf16Params {
     const float* x;                // [N][H][W][C] fp32
@@ -43,12 +35,6 @@ struct Bf16Params {
     FastDiv div_img, div_row;      // OH*OW, OW
     unsigned x_bytes, w_bytes;
 };
-
-// 2 fp32 -> 2 bf16 in one dword (v_cvt_pk_bf16_f32, round to nearest-even)
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void conv_bf16_kernel(const Bf16Params p) {
@@ -209,29 +195,6 @@ __global__ __launch_bounds__(256) void filter_to_bf16_kernel(const float* __rest
     }
 }
 
-int ilog2_exact(int v) {
-    if (v <= 0) return -1;
-    int s = 0;
-    while ((1 << s) < v) s++;
-    return ((1 << s) == v) ? s : -1;
-}
-
-int check_bf16(int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW) {
-    DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "conv_fwd_bf16: non-positive dimension");
-    DENET_CHECK_ARG(C % 32 == 0, "conv_fwd_bf16: physical C (%d) must be a multiple of 32", C);
-    DENET_CHECK_ARG(K % 32 == 0, "conv_fwd_bf16: physical K (%d) must be a multiple of 32", K);
-    DENET_CHECK_ARG(R == S && S_real == S, "conv_fwd_bf16: square filters with every tap real (R %d, S %d, S_real %d)", R, S, S_real);
-    DENET_CHECK_ARG(ilog2_exact(stride) >= 0, "conv_fwd_bf16: stride must be a power of two (got %d)", stride);
-    DENET_CHECK_ARG(pad >= 0, "conv_fwd_bf16: negative pad");
-    DENET_CHECK_ARG(H + 2 * pad >= R && OH > 0 && (H + 2 * pad - R) / stride + 1 >= OH, "conv_fwd_bf16: OH=%d inconsistent", OH);
-    DENET_CHECK_ARG(W + 2 * pad >= S && OW > 0 && (W + 2 * pad - S) / stride + 1 >= OW, "conv_fwd_bf16: OW=%d inconsistent", OW);
-    // operands are addressed through 32-bit buffer descriptors (byte offsets); 0xF0000000 is the out-of-range marker
-    DENET_CHECK_ARG((long)N * H * W * C * 4 < 0xF0000000L && (long)N * OH * OW * K * 4 < 0xF0000000L &&
-                        (long)K * R * S * C * 4 < 0xF0000000L,
-                    "conv_fwd_bf16: tensor exceeds the 32-bit buffer extent (3.75 GiB)");
-    return DENET_OK;
-}
-
 template <int BN>
 int launch_bf16(Bf16Params& p, hipStream_t stream) {
     constexpr int BM = 128;
@@ -258,7 +221,7 @@ extern "C" int denet_filter_to_bf16(const float* w, void* w16, long n, hipStream
 extern "C" int denet_conv_fwd_bf16(const float* x, const void* w16, const float* bias, const float* add, float* y, int relu, int N,
                                    int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW,
                                    hipStream_t stream) {
-    int rc = check_bf16(N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
+    int rc = check_conv_bf16("conv_fwd_bf16", N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
     if (rc) return rc;
     DENET_CHECK_ARG(x && w16 && y, "conv_fwd_bf16: null tensor");
     Bf16Params p = {};

@@ -16,19 +16,13 @@
 //   Zeros:     padding taps, pixels beyond N*OH*OW, filter rows beyond K and columns beyond R*S*C are staged as +0.
 //   Slices:    the chunks are cut into slices by wgrad_slices (geometry only, at most 128); a slice writes its partial dw to the
 //              workspace and conv_bf16_wgrad_reduce_kernel adds them in slice order. No atomics: bit-identical run to run.
-#include "common.h"
+#include "bf16_mma.h"
 #include "../../include/denet_hip.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BK = 32;                                // pixels per chunk
 constexpr int BN = 128;                               // columns of R*S*C per tile
-constexpr int ROWB = 80;                              // bytes per LDS row: 32 bf16 + 16 bytes of padding
-constexpr int OOBV = (int)0xF0000000u;                // beyond every extent check_train admits: the lane reads 0
 
 struct WgradParams {
     const float* x;                // [N][H][W][C] fp32
@@ -44,12 +38,6 @@ struct WgradParams {
     FastDiv div_img, div_row, div_c, div_s;      // OH*OW, OW, C, S
     unsigned x_bytes, dy_bytes;
 };
-
-// 2 fp32 -> 2 bf16 in one dword (v_cvt_pk_bf16_f32, round to nearest-even)
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 
 template <int BM, int BNT>
 __global__ __launch_bounds__(256) void conv_bf16_wgrad_kernel(const WgradParams p) {
@@ -261,30 +249,6 @@ __global__ __launch_bounds__(256) void filter_to_bf16_dgrad_kernel(const float* 
     }
 }
 
-int ilog2_exact(int v) {
-    if (v <= 0) return -1;
-    int s = 0;
-    while ((1 << s) < v) s++;
-    return ((1 << s) == v) ? s : -1;
-}
-
-// the geometry rules of conv_bf16.hip's forward kernel, reported under the caller's name
-int check_train(const char* who, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW) {
-    DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "%s: non-positive dimension", who);
-    DENET_CHECK_ARG(C % 32 == 0, "%s: physical C (%d) must be a multiple of 32", who, C);
-    DENET_CHECK_ARG(K % 32 == 0, "%s: physical K (%d) must be a multiple of 32", who, K);
-    DENET_CHECK_ARG(R == S && S_real == S, "%s: square filters with every tap real (R %d, S %d, S_real %d)", who, R, S, S_real);
-    DENET_CHECK_ARG(ilog2_exact(stride) >= 0, "%s: stride must be a power of two (got %d)", who, stride);
-    DENET_CHECK_ARG(pad >= 0, "%s: negative pad", who);
-    DENET_CHECK_ARG(H + 2 * pad >= R && OH > 0 && (H + 2 * pad - R) / stride + 1 >= OH, "%s: OH=%d inconsistent", who, OH);
-    DENET_CHECK_ARG(W + 2 * pad >= S && OW > 0 && (W + 2 * pad - S) / stride + 1 >= OW, "%s: OW=%d inconsistent", who, OW);
-    // operands are addressed through 32-bit buffer descriptors (byte offsets); 0xF0000000 is the out-of-range marker
-    DENET_CHECK_ARG((long)N * H * W * C * 4 < 0xF0000000L && (long)N * OH * OW * K * 4 < 0xF0000000L &&
-                        (long)K * R * S * C * 4 < 0xF0000000L,
-                    "%s: tensor exceeds the 32-bit buffer extent (3.75 GiB)", who);
-    return DENET_OK;
-}
-
 int wgrad_bm(int K) { return K >= 96 ? 128 : (K >= 64 ? 64 : 32); }
 
 // slices of the filter gradient's pixel reduction, from the geometry alone (conv_rect.hip's rule): enough workgroups for two per
@@ -331,7 +295,7 @@ extern "C" int denet_filter_to_bf16_dgrad(const float* w, void* wt16, int K, int
 
 extern "C" int denet_conv_dgrad_bf16(const float* dy, const void* wt16, const float* add, float* dx, int N, int H, int W, int C, int K,
                                      int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream) {
-    int rc = check_train("conv_dgrad_bf16", N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
+    int rc = check_conv_bf16("conv_dgrad_bf16", N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
     if (rc) return rc;
     DENET_CHECK_ARG(stride == 1, "conv_dgrad_bf16: stride 1 only (got %d): a strided data gradient runs the fp32 kernels", stride);
     DENET_CHECK_ARG(pad <= R - 1, "conv_dgrad_bf16: pad (%d) must not exceed R - 1 (%d)", pad, R - 1);
@@ -355,7 +319,7 @@ extern "C" size_t denet_conv_wgrad_bf16_workspace_bytes(int N, int C, int K, int
 extern "C" int denet_conv_wgrad_bf16(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N,
                                      int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW,
                                      hipStream_t stream) {
-    int rc = check_train("conv_wgrad_bf16", N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
+    int rc = check_conv_bf16("conv_wgrad_bf16", N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
     if (rc) return rc;
     DENET_CHECK_ARG(x && dy && dw, "conv_wgrad_bf16: null tensor");
     WgradParams p = {};

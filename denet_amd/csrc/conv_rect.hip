@@ -366,13 +366,6 @@ __global__ __launch_bounds__(256) void conv_rect_reduce_kernel(const float* __re
     ((f32x4*)out)[col] = s;
 }
 
-int ilog2_exact(int v) {
-    if (v <= 0) return -1;
-    int s = 0;
-    while ((1 << s) < v) s++;
-    return ((1 << s) == v) ? s : -1;
-}
-
 int check_rect(const char* who, int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
                int OW) {
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "%s: non-positive dimension", who);

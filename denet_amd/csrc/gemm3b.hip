@@ -11,19 +11,12 @@
 // Tile 128 x 128 x 32, 256 threads = 2 x 2 waves of 64 x 64; fp32 operands are loaded to registers (the next K block while
 // this one is multiplied), split, and written to LDS as four bf16 images (A_hi, A_lo, B_hi, B_lo; rows padded to 80 bytes:
 // the 16-byte fragment reads of 16 consecutive rows cover all 64 banks).
-#include "common.h"
+#include "bf16_mma.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128, BN = 128, BK = 32;
-constexpr int ROWB = 80;                              // bytes per LDS row: 32 bf16 + 16 bytes of padding
 constexpr int IMG = BM * ROWB;                        // one bf16 image of a 128 x 32 tile
-constexpr int OOBV = (int)0xF0000000u;
 
 struct G3Params {
     const float* a;      // [M][K]
@@ -74,7 +67,6 @@ __global__ __launch_bounds__(256, 3) void gemm3b_nt_kernel(const G3Params p) {
             gb[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, b_off + (32 * i * p.K + k0) * 4, 0, 0));
         }
     };
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     auto stage = [&]() {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

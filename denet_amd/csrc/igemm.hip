@@ -972,12 +972,6 @@ Choice choose_launch(const long* nblocks, const double* area, const double* eff,
     return best;
 }
 
-int ilog2_exact(int v) {
-    int s = 0;
-    while ((1 << s) < v) s++;
-    return ((1 << s) == v) ? s : -1;
-}
-
 int check_geom(int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW) {
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "conv: non-positive dimension");
     DENET_CHECK_ARG(S_real > 0 && S_real <= S, "conv: S_real out of range");

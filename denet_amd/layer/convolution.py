@@ -183,14 +183,7 @@ class ConvLayer(AbstractLayer):
         # inside its input transform; whatever path conv_fwd takes, the activation exists afterwards and is stored back
         link = self.input.take_pending_data()
         cache = self._cache()
-        cache["train"] = bool(get_train()) and self.enabled and self.omega.grad is not None
-        # an inference pass (never a pass of a training step, frozen layers included) may take the opt-in bf16 kernel
-        # (ops.INFER_PRECISION) unless the layer is kept in fp32 (fp32_only: a softmax reads this layer's output)
-        cache["infer"] = not get_train()
-        cache["fp32_only"] = getattr(self, "fp32_only", False)
-        # a training-mode pass of an eligible layer takes the opt-in bf16 kernels (ops.TRAIN_PRECISION); the mode is recorded here,
-        # and the backward pass of this step follows the record whatever the global says by then
-        bf16 = cache["bf16_train"] = bool(get_train()) and ops.train_bf16() and self._bf16_train_eligible()
+        bf16 = self._record_mode(cache, bool(get_train()))
         if bf16 and ops.HEAD_BF16X3:
             raise ValueError(ops.BF16_CONFLICT)   # (also for a model whose build_train_func ran before the mode was switched on)
         # a batch norm directly behind this layer (it flags its input Act) gets its statistics from this pass's epilogue (never the
@@ -242,6 +235,19 @@ class ConvLayer(AbstractLayer):
         self._settle_up(up)
         self.output.stats = cache.pop("bn_stats", None) if want_stats else None
 
+    def _record_mode(self, cache, training):
+        """what ops.conv_fwd / conv_dgrad / conv_wgrad read about this pass in the layer's cache -> cache["bf16_train"]"""
+        cache["train"] = training and self.enabled and self.omega.grad is not None
+        # an inference pass (never a pass of a training step, frozen layers included) may take the opt-in bf16 kernel
+        # (ops.INFER_PRECISION) unless the layer is kept in fp32 (fp32_only: a softmax reads this layer's output)
+        cache["infer"] = not training
+        cache["fp32_only"] = getattr(self, "fp32_only", False)
+        # a training-mode pass of an eligible layer takes the opt-in bf16 kernels (ops.TRAIN_PRECISION); the mode is recorded here,
+        # and the backward pass of this step follows the record whatever the global says by then. (What a training step recorded
+        # is that step's: inference never reads TRAIN_PRECISION)
+        cache["bf16_train"] = training and ops.train_bf16() and self._bf16_train_eligible()
+        return cache["bf16_train"]
+
     def _bf16_train_eligible(self):
         """the layers ops.TRAIN_PRECISION = "bf16" moves ("bf16 training"): square, not anisotropic, 32 physical input
         channels or more (never the stem), every tap real, a stride that is a power of two (the bf16 kernels take no other), no cut
@@ -265,10 +271,7 @@ class ConvLayer(AbstractLayer):
         """inference only: this convolution with the batch-norm layer behind it folded into its filters (recomputed
         when the weights change), residual `add` and ReLU in the epilogue; writes the batch norm's output"""
         cache = self._cache()
-        cache["train"] = False
-        cache["infer"] = True
-        cache["fp32_only"] = getattr(self, "fp32_only", False)
-        cache["bf16_train"] = False            # (what a training step recorded is that step's: inference never reads TRAIN_PRECISION)
+        self._record_mode(cache, False)
         ent = cache.get("fold")
         if ent is None or ent[0] != ops.WEIGHTS_VERSION or ent[1] is not bn:
             w_f, b_f = ops.bn_fold(self._w(), self.beta.dev if self.use_bias else None, bn.omega.dev, bn.beta.dev,

@@ -586,32 +586,32 @@ def conv_fwd(x, w, bias=None, add=None, stride=1, pad=0, s_real=None, out=None, 
     cache["bn_stats"] = (partial sums tensor, rows) for bn_fwd_train(pre=...), or None when the chosen kernel cannot.
     link (BnLink, x = None): the input is the output of a batch norm whose pointwise pass has not run; a Winograd pass evaluates
     it inside its input transform, every other implementation materialises it first. link.result is the activation afterwards."""
-    if INFER_PRECISION != "fp32" and cache is not None and cache.get("infer") and not cache.get("train") and not bn_stats \
-            and not cache.get("fp32_only") and _check_precision(INFER_PRECISION) == "bf16":
-        # OPT-IN bf16 inference (csrc/conv_bf16.hip): an inference pass of a layer that is not kept in fp32 (ConvLayer.fp32_only);
-        # a geometry the kernel does not take (fewer than 32 channels) falls through to the fp32 kernels
+    # OPT-IN bf16 (csrc/conv_bf16.hip). Inference: a pass of a layer that is not kept in fp32 (ConvLayer.fp32_only). Training:
+    # ConvLayer.forward recorded the mode for this step; never an inference pass, whatever an earlier training step left in the
+    # layer's cache
+    infer16 = INFER_PRECISION != "fp32" and cache is not None and cache.get("infer") and not cache.get("train") and not bn_stats \
+        and not cache.get("fp32_only") and infer_bf16()
+    train16 = not infer16 and cache is not None and cache.get("bf16_train") and not cache.get("infer")
+    if infer16 or train16:
+        assert infer16 or (not bn_stats and not relu)
         xs = link.x.shape if link is not None else (up.shape if up is not None else x.shape)
         g = conv_geom(xs, w.shape, stride, pad, s_real, ohw)
-        if g[3] % 32 == 0 and g[5] == g[6] == g[7]:
+        # an inference geometry the kernel does not take (fewer than 32 channels) falls through to the fp32 kernels; a training one
+        # was the layer's to judge (ConvLayer._bf16_train_eligible)
+        if train16 or (g[3] % 32 == 0 and g[5] == g[6] == g[7]):
             if link is not None:
-                x = link.materialise()
+                x = link.materialise()           # a pending input is written first
             if up is not None:
                 x = up.materialise()
-            return _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu)
-    if cache is not None and cache.get("bf16_train") and not cache.get("infer"):
-        # OPT-IN bf16 training (ConvLayer.forward recorded the mode for this step; never an inference pass, whatever an earlier
-        # training step left in the layer's cache): the bf16 kernel on the raw filter, a pending
-        # input written first, no statistics in the epilogue - the batch norm behind measures its own
-        assert not bn_stats and not relu
-        if link is not None:
-            x = link.materialise()
-        if up is not None:
-            x = up.materialise()
-        g = conv_geom(x.shape, w.shape, stride, pad, s_real, ohw)
-        cache["bn_stats"] = None
-        _note_fwd_tile(cache, 0)
-        cache["fwd_tile_train"] = 0            # (no Winograd filters for wino_prefetch_filters to prepare, trained or frozen)
-        return _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, False, key="w16_train")
+            if train16:
+                cache["bn_stats"] = None           # no statistics in the epilogue: the batch norm behind measures its own
+                _note_fwd_tile(cache, 0)
+                cache["fwd_tile_train"] = 0        # (no Winograd filters for wino_prefetch_filters to prepare, trained or frozen)
+            w16 = _bf16_filter(cache, "w16_train" if train16 else "w16", w, filter_to_bf16)
+            y = _launch_conv_fwd_bf16(x, w16, bias, add, g, out, relu)
+            if PROFILE is not None:
+                PROFILE.add(_conv_flops(g, logical))
+            return y
     if link is not None:
         g = conv_geom(link.x.shape, w.shape, stride, pad, s_real, ohw)
         tile = _decided(0, g)
@@ -1158,13 +1158,11 @@ def conv_dgrad(dy, w, x_shape, add=None, stride=1, pad=0, s_real=None, out=None,
         # OPT-IN bf16 training: the forward kernel on dy over the rotated, transposed bf16 filter (made once per weights version);
         # no backward sums - the batch norm in front does its own reductions. A strided layer falls through to the fp32 kernels
         assert sums is None
-        ent = cache.get("w16_dgrad")
-        if ent is None or ent[0] != WEIGHTS_VERSION or ent[1] != w.data_ptr() or ent[2].shape != (g[3], g[5], g[6], g[4]):
-            ent = cache["w16_dgrad"] = (WEIGHTS_VERSION, w.data_ptr(), filter_to_bf16_dgrad(w), w)
+        wt16 = _bf16_filter(cache, "w16_dgrad", w, filter_to_bf16_dgrad)
         cache["dgrad_tile"] = 0
         for k in ("dgrad_1x1t", "dgrad_t", "dgrad_s2"):      # (nothing for wino_prefetch_filters to prepare for this layer)
             cache.pop(k, None)
-        check(_L().denet_conv_dgrad_bf16(ptr(dy), ptr(ent[2]), ptr(add), ptr(dx), *g, stream_ptr()), "conv_dgrad_bf16")
+        conv_dgrad_bf16(dy, wt16, x_shape, add=add, pad=pad, out=dx)       # (conv_dgrad_bf16_ok: the geometry it derives is g)
         if PROFILE is not None:
             PROFILE.add(_conv_flops(g, logical))
         return dx
@@ -1638,24 +1636,33 @@ PRECISIONS = ("fp32", "bf16")
 INFER_PRECISION = "bf16" if os.environ.get("DENET_INFER_BF16", "0") not in ("0", "") else "fp32"
 
 
-def _check_precision(name):
+def _precision(what, name):
+    """`name` when it is one of PRECISIONS; what = "inference" / "training" """
     if name not in PRECISIONS:
-        raise ValueError("inference precision %r: expected one of %s" % (name, ", ".join(PRECISIONS)))
+        raise ValueError("%s precision %r: expected one of %s" % (what, name, ", ".join(PRECISIONS)))
     return name
 
 
 @contextlib.contextmanager
-def infer_precision(name):
-    """INFER_PRECISION set to `name` ("fp32" / "bf16", anything else raises ValueError) inside the block, restored on the way
-    out. Only inference passes read it: training and model-update-bn (which forces "fp32") never take the bf16 kernel"""
-    global INFER_PRECISION
-    _check_precision(name)
-    was = INFER_PRECISION
-    INFER_PRECISION = name
+def _precision_block(var, what, name):
+    """the module global `var` (INFER_PRECISION / TRAIN_PRECISION) set to `name` inside the block, restored on the way out"""
+    was = globals()[var]
+    globals()[var] = _precision(what, name)
     try:
         yield
     finally:
-        INFER_PRECISION = was
+        globals()[var] = was
+
+
+def infer_precision(name):
+    """INFER_PRECISION set to `name` ("fp32" / "bf16", anything else raises ValueError) inside the block, restored on the way
+    out. Only inference passes read it: training and model-update-bn (which forces "fp32") never take the bf16 kernel"""
+    return _precision_block("INFER_PRECISION", "inference", name)
+
+
+def infer_bf16():
+    """True while inference passes take the bf16 kernel; a value that is neither name raises where it is read"""
+    return _precision("inference", INFER_PRECISION) == "bf16"
 
 
 def filter_to_bf16(w):
@@ -1667,25 +1674,24 @@ def filter_to_bf16(w):
 
 def conv_fwd_bf16(x, w16, bias=None, add=None, stride=1, pad=0, out=None, relu=False, ohw=None):
     """y = epilogue(conv(bf16(x), w16)) accumulated in fp32: x fp32 NHWC (rounded when staged), w16 = filter_to_bf16(filter)"""
-    g = conv_geom(x.shape, w16.shape, stride, pad, None, ohw)
+    return _launch_conv_fwd_bf16(x, w16, bias, add, conv_geom(x.shape, w16.shape, stride, pad, None, ohw), out, relu)
+
+
+def _launch_conv_fwd_bf16(x, w16, bias, add, g, out, relu):
+    """the kernel under a geometry the caller worked out (conv_fwd_bf16; conv_fwd's bf16 branch, whose g carries the layer's s_real)"""
     y = out if out is not None else empty(g[0], g[10], g[11], g[4])
     check(_L().denet_conv_fwd_bf16(ptr(x), ptr(w16), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_fwd_bf16")
     return y
 
 
-def _conv_fwd_bf16(x, w, bias, add, g, out, logical, cache, relu, key="w16"):
-    """conv_fwd's bf16 branches: the bf16 filter is made once per weights version and per filter tensor (inference, key "w16": the
-    folded one of ConvLayer.forward_folded or the layer's own; training, key "w16_train": the raw one), kept in the layer's cache
-    like cache["fold"] / cache["u_test"]"""
+def _bf16_filter(cache, key, w, make):
+    """the bf16 copy make(w) of the filter w, made once per weights version and per filter tensor and kept in the layer's cache like
+    cache["fold"] / cache["u_test"]. Inference, key "w16": the folded filter of ConvLayer.forward_folded or the layer's own;
+    training, "w16_train": the raw one, and "w16_dgrad": its rotated, transposed copy (filter_to_bf16_dgrad)"""
     ent = cache.get(key)
-    if ent is None or ent[0] != WEIGHTS_VERSION or ent[1] != w.data_ptr() or ent[2].shape != w.shape:
-        ent = cache[key] = (WEIGHTS_VERSION, w.data_ptr(), filter_to_bf16(w), w)        # (w is held: its address stays its own)
-    N, H, W, C, K, R, S, s_real, stride, pad, OH, OW = g
-    y = out if out is not None else empty(N, OH, OW, K)
-    check(_L().denet_conv_fwd_bf16(ptr(x), ptr(ent[2]), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_fwd_bf16")
-    if PROFILE is not None:
-        PROFILE.add(_conv_flops(g, logical))
-    return y
+    if ent is None or ent[0] != WEIGHTS_VERSION or ent[1] != w.data_ptr() or ent[3].shape != w.shape:
+        ent = cache[key] = (WEIGHTS_VERSION, w.data_ptr(), make(w), w)        # (w is held: its address stays its own)
+    return ent[2]
 
 
 # OPT-IN, never the headline (bench.py never sets it): the eligible convolutions of a TRAINING step with both operands rounded to
@@ -1697,26 +1703,15 @@ BF16_CONFLICT = ("bf16 training (ops.TRAIN_PRECISION / DENET_TRAIN_BF16) and DEN
                  "same layers: choose one")
 
 
-@contextlib.contextmanager
 def train_precision(name):
     """TRAIN_PRECISION set to `name` ("fp32" / "bf16", anything else raises ValueError) inside the block, restored on the way out.
     Only training-mode passes read it"""
-    global TRAIN_PRECISION
-    if name not in PRECISIONS:
-        raise ValueError("training precision %r: expected one of %s" % (name, ", ".join(PRECISIONS)))
-    was = TRAIN_PRECISION
-    TRAIN_PRECISION = name
-    try:
-        yield
-    finally:
-        TRAIN_PRECISION = was
+    return _precision_block("TRAIN_PRECISION", "training", name)
 
 
 def train_bf16():
     """True while training-mode passes take the bf16 kernels; a value that is neither name raises where it is read"""
-    if TRAIN_PRECISION not in PRECISIONS:
-        raise ValueError("training precision %r: expected one of %s" % (TRAIN_PRECISION, ", ".join(PRECISIONS)))
-    return TRAIN_PRECISION == "bf16"
+    return _precision("training", TRAIN_PRECISION) == "bf16"
 
 
 def filter_to_bf16_dgrad(w):

@@ -1,61 +1,18 @@
 """Opt-in bf16 inference (ops.INFER_PRECISION = "bf16", csrc/conv_bf16.hip) on the device.
 
-The numerics contract ("bf16 inference"): an eligible convolution computes
-    y = epilogue( sum over taps and channels of bf16(x) * bf16(w_f) ),   accumulated in fp32,
-x and w_f rounded to nearest-even. The product of two bf16 values is exact in fp32, so the kernel differs from the same sum in
-fp64 ON THE ROUNDED OPERANDS only by its fp32 additions:
-    |y - y64| <= n * 2^-23 * T + 4 * 2^-24 * |y64|,      T = conv(|x_r|, |w_r|),  n = R*S*C
-(twice the worst case of n fp32 additions, plus the fp32 additions of the epilogue). The bound is derived, not measured: a dropped
-tap, a wrong channel or truncation instead of RNE on an operand misses it by orders of magnitude. The checker always rounds the
-very fp32 values the kernel rounds, so no value can fall on the other side of a rounding boundary."""
+The numerics contract ("bf16 inference") and the checker that states its bound - fp64 on the operands the kernel really
+multiplies - are in tests/bf16_reference.py."""
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+from bf16_reference import check_fwd, draw, ties
 from denet_amd import ops
 from denet_amd.model import audit, model_cnn, update_bn, zoo
 
 pytestmark = pytest.mark.gpu
 
 BF16 = "conv_bf16_kernel"
-
-
-# ------------------------------------------------------------------------------------------------------------------ the checker
-def _conv64(x, w, stride, pad, ohw):
-    """NHWC x [N][H][W][C], KRSC w (correlation taps, as the device stores them) -> NHWC float64"""
-    y = F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), stride=stride, padding=pad).permute(0, 2, 3, 1)
-    if ohw is not None:
-        y = y[:, :ohw[0], :ohw[1]]
-    return y.contiguous()
-
-
-def check_against_rounded_fp64(y, x, w, bias=None, add=None, relu=False, stride=1, pad=0, ohw=None, what=""):
-    """y (device result) against fp64 on the operands the kernel really multiplies; prints the figures, then asserts the bound"""
-    x, w, y = x.detach().cpu(), w.detach().cpu(), y.detach().cpu().double()
-    xr, wr = x.bfloat16().float().double(), w.bfloat16().float().double()
-    y64 = _conv64(xr, wr, stride, pad, ohw)
-    T = _conv64(xr.abs(), wr.abs(), stride, pad, ohw)
-    if bias is not None:
-        y64 = y64 + bias.detach().cpu().double()
-    if add is not None:
-        y64 = y64 + add.detach().cpu().double()
-    if relu:
-        y64 = y64.clamp_min(0.0)
-    assert y.shape == y64.shape, (y.shape, y64.shape)
-    n = w.shape[1] * w.shape[2] * w.shape[3]
-    bound = n * 2.0 ** -23 * T + 4 * 2.0 ** -24 * y64.abs()
-    err = (y - y64).abs()
-    worst = float((err / bound.clamp_min(1e-300)).max())
-    print("%s: n = %d, max |y - y64| = %.3e, max |y64| = %.3e, largest error / bound = %.3e"
-          % (what, n, float(err.max()), float(y64.abs().max()), worst))
-    assert torch.isfinite(y).all()
-    assert bool((err <= bound).all()), (what, worst)
-    assert float(y64.abs().max()) > 0
-
-
-def _draw(rng, *shape, scale=1.0):
-    return torch.from_numpy((rng.standard_normal(shape) * scale).astype(np.float32))
 
 
 # (N, H, W, C, K physical, K logical, filter, stride, pad, ohw, epilogue)
@@ -72,16 +29,16 @@ GEOMS = {
 def _operands(name):
     N, H, W, C, K, Kl, k, stride, pad, ohw, epi = GEOMS[name]
     rng = np.random.RandomState(sum(map(ord, name)))
-    x = _draw(rng, N, H, W, C)
-    w = _draw(rng, K, k, k, C, scale=(k * k * C) ** -0.5)
+    x = draw(rng, N, H, W, C)
+    w = draw(rng, K, k, k, C, scale=(k * k * C) ** -0.5)
     w[Kl:] = 0.0                                     # pad filters are zero, as Param packs them
     bias = add = None
     if epi or Kl != K:
-        bias = _draw(rng, K, scale=0.5)
+        bias = draw(rng, K, scale=0.5)
         bias[Kl:] = 0.0
     if epi:
         OH = (H + 2 * pad - k) // stride + 1
-        add = _draw(rng, N, OH, OH, K)
+        add = draw(rng, N, OH, OH, K)
     return x, w, bias, add
 
 
@@ -103,7 +60,7 @@ def test_kernel_against_fp64_on_the_rounded_operands(hip, name):
     (x, w, bias, add), y, w16 = _run(name)
     # the filter copy is the RNE rounding of the fp32 filter, bit for bit
     assert torch.equal(w16.cpu().view(torch.int16), w.bfloat16().view(torch.int16))
-    check_against_rounded_fp64(y, x, w, bias, add, relu=epi, stride=stride, pad=pad, ohw=ohw, what=name)
+    check_fwd(y, x, w, bias, add, relu=epi, stride=stride, pad=pad, ohw=ohw, what=name)
     if ohw is not None:
         assert tuple(y.shape[1:3]) == ohw
     if Kl != K:
@@ -116,13 +73,7 @@ def test_kernel_against_fp64_on_the_rounded_operands(hip, name):
 def test_operands_are_rounded_to_nearest_even_bit_for_bit(hip):
     """1x1 identity filter: y is the staged (rounded) x itself. Values exactly halfway between two bf16 neighbours (ties go to the
     even mantissa), and one fp32 ulp either side of them"""
-    ties = [1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8]
-    vals = []
-    for t in ties:
-        t32 = np.float32(t)
-        assert float(t32) == t
-        vals += [t32, np.nextafter(t32, np.float32(0)), np.nextafter(t32, np.float32(4))]
-    vals = np.array(vals + [-v for v in vals], dtype=np.float32)
+    vals = ties()
     rng = np.random.RandomState(3)
     x = rng.standard_normal((2, 5, 7, 32)).astype(np.float32)
     x.reshape(-1)[:: 3][:vals.size * 8] = np.tile(vals, 8)
@@ -130,8 +81,6 @@ def test_operands_are_rounded_to_nearest_even_bit_for_bit(hip):
     w = torch.eye(32).reshape(32, 1, 1, 32).contiguous()
     y = ops.conv_fwd_bf16(x.cuda(), ops.filter_to_bf16(w.cuda()))
     want = x.bfloat16().float()
-    # the reference itself rounds ties to even: 1 + 2^-8 -> 1, 1 + 3 * 2^-8 -> 1 + 2^-6
-    assert float(torch.tensor(ties[0]).bfloat16()) == 1.0 and float(torch.tensor(ties[1]).bfloat16()) == 1.0 + 2.0 ** -6
     assert torch.equal(y.cpu().view(torch.int32), want.view(torch.int32))
 
 
@@ -187,8 +136,8 @@ def test_model_layers_against_fp64_on_their_own_inputs(hip):
         ent = conv._cache()["fold"]
         bn = ent[1]
         relu = bn.type_name == "batchnorm-relu" or bool(getattr(bn, "act_fused", False))
-        check_against_rounded_fp64(conv.output.data, conv.input.data, ent[2], bias=ent[3], relu=relu, stride=conv.stride[0],
-                                   pad=conv.pad, ohw=conv.ohw, what="stack conv %d" % (i + 1))
+        check_fwd(conv.output.data, conv.input.data, ent[2], bias=ent[3], relu=relu, stride=conv.stride[0], pad=conv.pad,
+                  ohw=conv.ohw, what="stack conv %d" % (i + 1))
     # the distance to fp32 mode is reported, not asserted: rounding flips move a free-running comparison
     pr32 = model.predict_output_step(x)
     print("stack: max |p_bf16 - p_fp32| = %.3e" % float(np.abs(pr - pr32).max()))
@@ -211,14 +160,14 @@ def test_residual_blocks_run_on_the_bf16_kernel(hip):
     # the residual rides in the epilogue of the last convolution of each block: check that one against fp64 too
     blocks = [l for l in model.layers if l.type_name == "resnet"]
     pre = blocks[0]._main()[-1]
-    check_against_rounded_fp64(pre.output.data, pre.input.data, pre._w(), add=blocks[0].input.data, stride=1, pad=pre.pad,
-                               what="RSN last convolution (+ x)")
+    check_fwd(pre.output.data, pre.input.data, pre._w(), add=blocks[0].input.data, stride=1, pad=pre.pad,
+              what="RSN last convolution (+ x)")
     assert blocks[1].__dict__.get("_plan"), "the RSN.O block did not run its folded plan"
     last = [l for l in blocks[1]._main() if l.type_name == "conv"][-1]
     ent = last._cache()["fold"]
     sc = blocks[1]._shortcut()
-    check_against_rounded_fp64(last.output.data, last.input.data, ent[2], bias=ent[3], add=sc[-1].output.data, relu=True, stride=1,
-                               pad=last.pad, what="RSN.O last convolution (+ shortcut, ReLU)")
+    check_fwd(last.output.data, last.input.data, ent[2], bias=ent[3], add=sc[-1].output.data, relu=True, stride=1, pad=last.pad,
+              what="RSN.O last convolution (+ shortcut, ReLU)")
 
 
 # ------------------------------------------------------------------------------------------- 5: no leakage, no stale caches

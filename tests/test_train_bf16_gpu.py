@@ -1,22 +1,15 @@
 """Opt-in bf16 training (ops.TRAIN_PRECISION = "bf16", csrc/conv_bf16.hip + csrc/conv_bf16_train.hip) on the device.
 
-The numerics contract ("bf16 training"): an eligible convolution of a training-mode pass computes
-    y  = sum bf16(x)  * bf16(w) (+ bias, + add),      dx = sum bf16(dy) * bf16(w) (+ add),      dw = sum over pixels bf16(dy) * bf16(x),
-operands rounded to nearest-even, accumulated in fp32. The product of two bf16 values is exact in fp32, so a kernel differs from the
-same sum in fp64 ON THE ROUNDED OPERANDS only by its fp32 additions:
-    |err| <= n * 2^-23 * T + 4 * 2^-24 * |ref|,      T = the same sum over absolute values,
-    n = R*S*C (forward), R*S*K (data gradient), N*OH*OW + the number of slices (filter gradient)
-(twice the worst case of n fp32 additions, plus the fp32 additions of the epilogue). The bound is derived, not measured: a dropped
-tap, a wrong pixel or truncation instead of RNE misses it by orders of magnitude. The checkers (the one of
-tests/test_infer_bf16_gpu.py, restated for the two gradients) always round the very fp32 values the kernel rounds."""
+The numerics contract ("bf16 training") and the checkers that state its bound - fp64 on the operands a kernel really
+multiplies, for the forward pass and the two gradients - are in tests/bf16_reference.py."""
 import glob
 import os
 
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
+from bf16_reference import bits, check_dgrad, check_fwd, check_wgrad, draw, ties
 from denet_amd import ops
 from denet_amd.model import audit, model_cnn, zoo
 
@@ -26,90 +19,6 @@ FWD = "conv_bf16_kernel"
 WGRAD = "conv_bf16_wgrad_kernel"
 REDUCE = "conv_bf16_wgrad_reduce_kernel"
 COPY = "filter_to_bf16_dgrad_kernel"
-
-
-# ----------------------------------------------------------------------------------------------------------------- the checkers
-def _r64(t):
-    return t.detach().cpu().bfloat16().float().double()
-
-
-def _assert_bound(got, ref, T, n, what, nonzero=True):
-    got = got.detach().cpu().double()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    bound = n * 2.0 ** -23 * T + 4 * 2.0 ** -24 * ref.abs()
-    err = (got - ref).abs()
-    worst = float((err / bound.clamp_min(1e-300)).max())
-    print("%s: n = %d, max |err| = %.3e, max |ref| = %.3e, largest error / bound = %.3e"
-          % (what, n, float(err.max()), float(ref.abs().max()), worst))
-    assert torch.isfinite(got).all()
-    assert bool((err <= bound).all()), (what, worst)
-    assert float(ref.abs().max()) > 0 or not nonzero
-    return float(ref.abs().max()) > 0
-
-
-def _conv64(x, w, stride, pad):
-    """NHWC x, KRSC w (correlation taps, as the device stores them) -> NHWC float64"""
-    return F.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), stride=stride, padding=pad).permute(0, 2, 3, 1).contiguous()
-
-
-def check_fwd(y, x, w, bias=None, add=None, stride=1, pad=0, what=""):
-    xr, wr = _r64(x), _r64(w)
-    ref, T = _conv64(xr, wr, stride, pad), _conv64(xr.abs(), wr.abs(), stride, pad)
-    if bias is not None:
-        ref = ref + bias.detach().cpu().double()
-    if add is not None:
-        ref = ref + add.detach().cpu().double()
-    _assert_bound(y, ref, T, w.shape[1] * w.shape[2] * w.shape[3], what)
-
-
-def _dgrad64(dy, w, x_shape, stride, pad):
-    N, H, W, C = x_shape
-    R = w.shape[1]
-    oph, opw = H - ((dy.shape[1] - 1) * stride - 2 * pad + R), W - ((dy.shape[2] - 1) * stride - 2 * pad + R)
-    dx = F.conv_transpose2d(dy.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), stride=stride, padding=pad, output_padding=(oph, opw))
-    return dx.permute(0, 2, 3, 1).contiguous()
-
-
-def check_dgrad(dx, dy, w, x_shape, add=None, stride=1, pad=0, what="", nonzero=True):
-    dyr, wr = _r64(dy), _r64(w)
-    ref, T = _dgrad64(dyr, wr, x_shape, stride, pad), _dgrad64(dyr.abs(), wr.abs(), x_shape, stride, pad)
-    if add is not None:
-        ref = ref + add.detach().cpu().double()
-    return _assert_bound(dx, ref, T, w.shape[0] * w.shape[1] * w.shape[2], what, nonzero)
-
-
-def _wgrad64(x, dy, w_shape, stride, pad):
-    w0 = torch.zeros(w_shape, dtype=torch.float64, requires_grad=True)
-    y = _conv64(x, w0, stride, pad)
-    assert y.shape == dy.shape, (y.shape, dy.shape)
-    y.backward(dy)
-    return w0.grad.detach()
-
-
-def check_wgrad(dw, x, dy, stride=1, pad=0, slices=1, what="", nonzero=True):
-    xr, dyr = _r64(x), _r64(dy)
-    ref, T = _wgrad64(xr, dyr, tuple(dw.shape), stride, pad), _wgrad64(xr.abs(), dyr.abs(), tuple(dw.shape), stride, pad)
-    return _assert_bound(dw, ref, T, dy.shape[0] * dy.shape[1] * dy.shape[2] + slices, what, nonzero)
-
-
-def _draw(rng, *shape, scale=1.0):
-    return torch.from_numpy((rng.standard_normal(shape) * scale).astype(np.float32))
-
-
-def _bits(t):
-    return t.detach().contiguous().view(torch.int32)
-
-
-def _ties():
-    """values exactly halfway between two bf16 neighbours (ties go to the even mantissa), one fp32 ulp either side, both signs"""
-    ties = [1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8]
-    vals = []
-    for t in ties:
-        t32 = np.float32(t)
-        assert float(t32) == t
-        vals += [t32, np.nextafter(t32, np.float32(0)), np.nextafter(t32, np.float32(4))]
-    assert float(torch.tensor(ties[0]).bfloat16()) == 1.0 and float(torch.tensor(ties[1]).bfloat16()) == 1.0 + 2.0 ** -6
-    return np.array(vals + [-v for v in vals], dtype=np.float32)
 
 
 # ------------------------------------------------------------------------------------------------------ 1: the data gradient
@@ -129,12 +38,12 @@ def _dgrad_case(name):
     N, H, W, C, Cl, K, k, pad, with_add = DGRAD[name]
     rng = np.random.RandomState(sum(map(ord, name)))
     OH, OW = H + 2 * pad - k + 1, W + 2 * pad - k + 1
-    dy = _draw(rng, N, OH, OW, K)
-    w = _draw(rng, K, k, k, C, scale=(k * k * K) ** -0.5)
+    dy = draw(rng, N, OH, OW, K)
+    w = draw(rng, K, k, k, C, scale=(k * k * K) ** -0.5)
     w[..., Cl:] = 0.0                                # pad channels of a filter are zero, as Param packs them
     add = None
     if with_add:
-        add = _draw(rng, N, H, W, C)
+        add = draw(rng, N, H, W, C)
         add[..., Cl:] = 0.0
     wt = ops.filter_to_bf16_dgrad(w.cuda())
     dx = ops.conv_dgrad_bf16(dy.cuda(), wt, (N, H, W, C), add=None if add is None else add.cuda(), pad=pad)
@@ -151,19 +60,19 @@ def test_data_gradient_against_fp64_on_the_rounded_operands(hip, name):
     assert torch.equal(wt.cpu().view(torch.int16), want.view(torch.int16))
     check_dgrad(dx, dy, w, (N, H, W, C), add=add, stride=1, pad=pad, what="dgrad " + name)
     if Cl != C:
-        assert int(_bits(dx[..., Cl:]).abs().max()) == 0, "pad channels must be +0 (sign bit clear)"
+        assert int(bits(dx[..., Cl:]).abs().max()) == 0, "pad channels must be +0 (sign bit clear)"
         assert bool((dy < 0).any())
 
 
 def test_data_gradient_rounds_to_nearest_even_bit_for_bit(hip):
     """1x1 identity filter: dx is the staged (rounded) dy itself"""
-    vals = _ties()
+    vals = ties()
     dy = np.random.RandomState(3).standard_normal((2, 5, 7, 32)).astype(np.float32)
     dy.reshape(-1)[:: 3][:vals.size * 8] = np.tile(vals, 8)
     dy = torch.from_numpy(dy)
     w = torch.eye(32).reshape(32, 1, 1, 32).contiguous()
     dx = ops.conv_dgrad_bf16(dy.cuda(), ops.filter_to_bf16_dgrad(w.cuda()), (2, 5, 7, 32))
-    assert torch.equal(_bits(dx.cpu()), _bits(dy.bfloat16().float()))
+    assert torch.equal(bits(dx.cpu()), bits(dy.bfloat16().float()))
 
 
 # ---------------------------------------------------------------------------------------------------- 2: the filter gradient
@@ -184,8 +93,8 @@ def _wgrad_case(name):
     N, H, W, C, Cl, K, Kl, k, stride, pad, slices = WGRADS[name]
     rng = np.random.RandomState(sum(map(ord, name)))
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    x = _draw(rng, N, H, W, C)
-    dy = _draw(rng, N, OH, OW, K)
+    x = draw(rng, N, H, W, C)
+    dy = draw(rng, N, OH, OW, K)
     x[..., Cl:] = 0.0                                # pad channels of activations and gradients are +0
     dy[..., Kl:] = 0.0
     g = ops.conv_geom(x.shape, (K, k, k, C), stride, pad)
@@ -201,7 +110,7 @@ def test_filter_gradient_against_fp64_on_the_rounded_operands(hip, name):
     assert got_slices == slices, (name, got_slices)
     check_wgrad(dw, x, dy, stride=stride, pad=pad, slices=slices, what="wgrad " + name)
     if Kl != K:
-        assert not _bits(dw[Kl:]).any() and not _bits(dw[..., Cl:]).any(), "pad rows and columns must be exactly 0"
+        assert not bits(dw[Kl:]).any() and not bits(dw[..., Cl:]).any(), "pad rows and columns must be exactly 0"
         assert bool(dw[:Kl, ..., :Cl].abs().min() > 0)
 
 
@@ -217,21 +126,21 @@ def test_three_slices_case_has_a_ragged_last_slice(hip):
 
 def test_filter_gradient_rounds_to_nearest_even_bit_for_bit(hip):
     """one pixel, x = 1: dw[k][c] is the staged (rounded) dy[k] itself"""
-    vals = _ties()
+    vals = ties()
     dy = np.random.RandomState(4).standard_normal(32).astype(np.float32)
     dy[:vals.size] = vals
     dy = torch.from_numpy(dy).reshape(1, 1, 1, 32)
     x = torch.ones(1, 1, 1, 32)
     dw = ops.conv_wgrad_bf16(x.cuda(), dy.cuda(), (32, 1, 1, 32))
     want = dy.bfloat16().float().reshape(32, 1, 1, 1).expand(32, 1, 1, 32).contiguous()
-    assert torch.equal(_bits(dw.cpu()), _bits(want))
+    assert torch.equal(bits(dw.cpu()), bits(want))
 
 
 def test_two_calls_are_bit_identical(hip):
     a, b = _wgrad_case("three-slices-ragged"), _wgrad_case("three-slices-ragged")
-    assert torch.equal(_bits(a[2]), _bits(b[2]))
+    assert torch.equal(bits(a[2]), bits(b[2]))
     a, b = _dgrad_case("partial-tiles"), _dgrad_case("partial-tiles")
-    assert torch.equal(_bits(a[4]), _bits(b[4]))
+    assert torch.equal(bits(a[4]), bits(b[4]))
 
 
 # ------------------------------------------------------------------------------------------------ 3: a model, layer by layer
@@ -349,7 +258,7 @@ def test_stack_step_kernels_and_layers_against_fp64(hip, monkeypatch):
     # the recorded filter gradients are what the solver read
     convs = [l for _, l in audit.conv_layers(model)]
     for conv, r in zip(reversed(convs[1:4]), rec.wgrad):
-        assert torch.equal(_bits(conv.omega.grad.view(conv.omega.dev_shape)), _bits(r["dw"]))
+        assert torch.equal(bits(conv.omega.grad.view(conv.omega.dev_shape)), bits(r["dw"]))
 
 
 def test_nothing_is_prepared_for_passes_that_do_not_run(hip):
@@ -438,7 +347,7 @@ def test_residual_blocks_step_against_fp64(hip, monkeypatch):
 
 
 def _state(model):
-    return [_bits(model.P).cpu().numpy(), _bits(model.G).cpu().numpy()]
+    return [bits(model.P).cpu().numpy(), bits(model.G).cpu().numpy()]
 
 
 def _one_step(desc, precision, seed=5):
@@ -484,7 +393,7 @@ def _sweeps(model, x, metas, between=None):
             layer_mod.set_rng_seed(model.rng_seed)
         model.backward(ctx)
     torch.cuda.synchronize()
-    return [_bits(model.G).cpu().numpy(), _bits(model.cost_buf).cpu().numpy()], ka.table
+    return [bits(model.G).cpu().numpy(), bits(model.cost_buf).cpu().numpy()], ka.table
 
 
 def test_an_fp32_model_is_untouched_by_a_bf16_model_stepping_beside_it(hip):
