@@ -57,7 +57,8 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         self.corner_layer = common.find_layers(layers, "denet-corner", True)
         assert self.corner_layer is not None, "denet-corner layer required before spare layer!"
         # nms_threshold < 1 turns on apply_cluster (denet_sparse.cc:541-542): the device proposal then returns the
-        # 10 * sn^2 best candidates (the clustering input, :171-175) instead of sn^2 and the grouping runs on the host
+        # 10 * sn^2 best candidates (the clustering input, :171-175) instead of sn^2 and the grouping runs on the host - or,
+        # opt-in (ops.CLUSTER_DEVICE), on the device (csrc/cluster.hip), which hands an sn^2 list on like a layer without clustering
         self.cluster = self.nms_threshold < 1.0
         self.proposal_count = 10 * self.sample_num * self.sample_num if self.cluster else self.sample_num * self.sample_num
 
@@ -126,17 +127,33 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         # and waiting until the device has run the forward pass up to the corner map + the proposal), "build" = the host
         # part of build_samples (here only its epilogue: libm score, box arithmetic, optional clustering)
         timer = common.Timer()
-        B, S = self.batch_size, self.proposal_count
+        # the opt-in device clustering (read here, where the step's proposal is queued): the 10 * sn^2 candidates stay in a
+        # device staging buffer and the packed result is the clustered, sn^2 wide list - from here on an ordinary proposal
+        self._dev_clustered = self._cluster_on_device()
+        B, S = self.batch_size, self._list_width()
         words = B * S * 5 + B
-        if getattr(self, "_res_dev", None) is None:
-            self._res_dev = torch.empty(words, dtype=torch.int32, device="cuda")
-            self._res_host = torch.empty(words, dtype=torch.int32).pin_memory()
+        if getattr(self, "_res_dev", None) is None or self._res_dev.numel() != words:
+            # (one pair of buffers per width: a clustering layer whose mode changes between steps goes back to the pair it had)
+            sets = self.__dict__.setdefault("_res_sets", {})
+            if words not in sets:
+                sets[words] = (torch.empty(words, dtype=torch.int32, device="cuda"), torch.empty(words, dtype=torch.int32).pin_memory())
+            self._res_dev, self._res_host = sets[words]
+            self._res_counts = None
         r = self._res_dev
         box = r[:B * S * 4].view(B, S, 4)
         absd = r[B * S * 4:B * S * 5].view(torch.float32).view(B, S)
         count = r[B * S * 5:]
-        ops.build_samples(cl.corner_pr, float(self.corner_threshold), S, self.corner_max, int(self.local_max),
-                          out=(box, absd, count))
+        if self._dev_clustered:
+            P = self.proposal_count
+            st = self.__dict__.get("_stage_dev")
+            if st is None:
+                st = self._stage_dev = torch.empty(B * P * 5 + B, dtype=torch.int32, device="cuda")
+            staged = (st[:B * P * 4].view(B, P, 4), st[B * P * 4:B * P * 5].view(torch.float32).view(B, P), st[B * P * 5:])
+            ops.build_samples(cl.corner_pr, float(self.corner_threshold), P, self.corner_max, int(self.local_max), out=staged)
+            ops.cluster_samples_device(*staged, float(self.nms_threshold), S, cl.height, cl.width, out=(box, absd, count))
+        else:
+            ops.build_samples(cl.corner_pr, float(self.corner_threshold), S, self.corner_max, int(self.local_max),
+                              out=(box, absd, count))
         if store_shared:
             cl.sample_shared = cl.conv.output.data
         self._res_host.copy_(r, non_blocking=True)
@@ -168,11 +185,21 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
             return None, None
         return self._finish_samples(timer, raw_only)
 
+    _dev_clustered = False         # the proposal in flight was clustered on the device (set by _device_samples)
+
+    def _cluster_on_device(self):
+        """this layer clusters and the opt-in device form applies: mode on, a threshold the closed form covers, a device"""
+        return self.cluster and ops.CLUSTER_DEVICE and 0.0 <= self.nms_threshold < 1.0 and self._on_device()
+
+    def _list_width(self):
+        """rows per image of the packed result the device hands over: sn^2, or the 10 * sn^2 candidates the host will cluster"""
+        return self.sample_count if self._dev_clustered else self.proposal_count
+
     def _finish_samples(self, timer, raw_only, log=True):
         """host epilogue of the proposal: sample tuples from the packed result in the pinned buffer"""
         import torch
         cl = self.corner_layer
-        B, S = self.batch_size, self.proposal_count
+        B, S = self.batch_size, self._list_width()
         h = self._res_host
         hcount = h[B * S * 5:]
         if int(hcount.sum()) == 0:        # cold detector: nothing proposed
@@ -189,7 +216,7 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         ring[self._finish_turn] = out
         raw = out.numpy()
         hcount = hcount.numpy()
-        if self.cluster:
+        if self.cluster and not self._dev_clustered:
             raw, hcount = ops.cluster_samples_host(raw, hcount, self.nms_threshold, self.sample_count)
         self._raw_samples = (raw, hcount)
         if log:
@@ -332,7 +359,8 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         self._dev_edit = None
         if get_train() and self._native_edit_ok(metas) and _RH.PREFETCH_RANDOM:
             self._prefetch_random()
-            if _RH.DEVICE_EDIT and self._on_device() and not self.cluster:
+            # (the device-side editing reads an sn^2 wide hand-off list: no clustering, or clustering on the device)
+            if _RH.DEVICE_EDIT and self._on_device() and (not self.cluster or self._cluster_on_device()):
                 self._upload_for_device_edit(metas, prep)
 
     _ON_DEVICE = None

@@ -16,7 +16,7 @@ from .. import ops
 # The RoI hand-off (device proposal -> edited bbox array -> gather) has two short forms and the ordinary host path:
 #   device_edit  no image proposes more RoIs than the list keeps (no random.sample): the bbox array is written on the device
 #   fast         any other batch: ONE native host call writes the bbox array, its bookkeeping runs beside the gather
-#   host         what remains (clustering, coverage logging, a generator that moved, CPU runs): edit + upload on the host
+#   host         what remains (clustering on the host, coverage logging, a generator that moved, CPU runs): edit + upload on the host
 # DENET_SHORT_HANDOFF=0 is the one switch: the ordinary path only. The three names below are test hooks, not configuration.
 SHORT_HANDOFF = os.environ.get("DENET_SHORT_HANDOFF", "1") != "0"
 PREFETCH_RANDOM = DEVICE_EDIT = FAST_HANDOFF = SHORT_HANDOFF
@@ -159,7 +159,8 @@ class RoiHandoff:
         here and the hand-off draws from the generator: the host only waits): the prefetched stretch, the prepared ground truth,
         a generator that has not moved since. (pf, prep) or None"""
         pf, prep = self.__dict__.get("_prefetch"), self.__dict__.get("_prep")
-        if pf is None or prep is None or self.cluster or self.proposal_count != self.sample_count or not self._on_device():
+        # (the short forms read an sn^2 wide hand-off list: a clustering layer has one only when it clustered on the device)
+        if pf is None or prep is None or self._list_width() != self.sample_count or not self._on_device():
             return None
         if not (DEVICE_EDIT or FAST_HANDOFF) or not pf["mirror"].fresh():
             return None

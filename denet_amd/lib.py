@@ -184,6 +184,8 @@ SIGNATURES = {
     "denet_edit_samples_device": (I, [P, P, I, I, P, L, L, P, P] + [I] * 4 + [P, P, P]),
     "denet_host_cluster_samples": (I, [P, I, F, I, P, P]),
     "denet_samples_finish_host": (I, [P, P, P, I, I, I, I, P]),
+    "denet_cluster_samples_workspace_bytes": (Z, [I, I]),
+    "denet_cluster_samples_device": (I, [P, P, P, I, I, F, I, I, I, P, P, P, P, Z, P]),
 }
 
 

@@ -142,6 +142,9 @@ def build_parser():
     parser.add_argument("--params", default="", type=str, help="Additional detection params")
     parser.add_argument("--device-render", default=False, action="store_true",
                         help="detect mode: scale / crop the images on the GPU instead of in the loader processes")
+    parser.add_argument("--device-cluster", default=False, action="store_true",
+                        help="opt-in: DNS layers with 0 <= nmsThreshold < 1 cluster their RoI candidates on the GPU instead of in host "
+                             "code (csrc/cluster.hip); equal results on proposals without tied scores, ties are broken by rank")
     from .. import ops
     parser.add_argument("--precision", default=ops.INFER_PRECISION, choices=ops.PRECISIONS,
                         help="arithmetic of the inference convolutions, every predict mode: fp32 (the default, exact) or bf16 (opt-in: "
@@ -157,7 +160,9 @@ def main(argv=None):
     model = model_cnn.load_from_file(args.model, args.batch_size)
     data = dataset.load(args.input, args.extension, class_labels=model.class_labels, thread_num=args.thread_num)
     from .. import ops
-    with ops.infer_precision(args.precision):
+    with ops.infer_precision(args.precision), ops.cluster_device(args.device_cluster or ops.CLUSTER_DEVICE):
+        if ops.CLUSTER_DEVICE:
+            logging.info("RoI clustering runs on the device (--device-cluster): ties of equal scores are broken by rank")
         if "single" in args.predict_mode:
             test_single(args.predict_mode, model, data)
         elif "multicrop" in args.predict_mode:

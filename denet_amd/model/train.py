@@ -102,6 +102,9 @@ def build_parser(single=True):
     parser.add_argument("--device-render", default=False, action="store_true",
                         help="render the augmentation (crop, resampling, colour jitter) on the GPU instead of in the loader "
                              "processes: same batches, one host process per GPU keeps up with training")
+    parser.add_argument("--device-cluster", default=False, action="store_true",
+                        help="opt-in: DNS layers with 0 <= nmsThreshold < 1 cluster their RoI candidates on the GPU instead of in host "
+                             "code (csrc/cluster.hip); equal results on proposals without tied scores, ties are broken by rank")
     parser.add_argument("--border-mode", default="valid")
     parser.add_argument("--output-prefix", default="./model")
     parser.add_argument("--activation", default="relu")
@@ -218,7 +221,9 @@ def main(argv=None):
     if args.test:
         test_data = load_dataset(args.test, args.seed, args.extension, False, args.thread_num, train_data.class_labels)
     from .. import ops
-    with ops.train_precision(args.precision):
+    with ops.train_precision(args.precision), ops.cluster_device(args.device_cluster or ops.CLUSTER_DEVICE):
+        if ops.CLUSTER_DEVICE:
+            logging.info("RoI clustering runs on the device (--device-cluster): ties of equal scores are broken by rank")
         train(args, train_data, test_data=test_data)
     return 0
 

@@ -180,7 +180,9 @@ def main(argv=None):
     if not hasattr(data, "images"):
         raise SystemExit("model-train-multi shards the image list of an MSCOCO / Pascal VOC / ImageNet dataset")
     from .. import ops
-    with ops.train_precision(args.precision):
+    with ops.train_precision(args.precision), ops.cluster_device(args.device_cluster or ops.CLUSTER_DEVICE):
+        if ops.CLUSTER_DEVICE:
+            logging.info("RoI clustering runs on the device (--device-cluster): ties of equal scores are broken by rank")
         train(args, data, dp)
     if hasattr(data, "image_loader"):
         data.image_loader.close()

@@ -58,7 +58,8 @@ def kernel_symbol(kind, a, b, c):
     if kind == 22:
         return "conv_bf16_wgrad_kernel<%d, %d>" % (a, b)       # tile BM x BN of the opt-in bf16 filter gradient
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
-             24: "filter_to_bf16_dgrad_kernel"}.get(kind)
+             24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
+             33: "cluster_select_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
 
@@ -2312,6 +2313,49 @@ def cluster_samples_host(raw, counts, threshold, output_num):
             out[b, :n] = raw[b, :n]
             out_counts[b] = n
     return out, out_counts
+
+
+# OPT-IN (bench.py never sets it): a DNS layer with 0 <= nmsThreshold < 1 clusters its 10 * sn^2 candidates ON THE DEVICE
+# (csrc/cluster.hip; the closed form and the tie rule are in DESIGN.md, "RoI clustering on the device") and hands an ordinary sn^2
+# proposal on. Off, the product default: the host routine (cluster_samples_host). Ties of the fp32 score are broken by rank on the
+# device and by member order on the host - each valid under the reference; on tie-free proposals the two agree row for row.
+# DeNetSparseLayer reads it when it queues a step's proposal
+CLUSTER_DEVICE = os.environ.get("DENET_CLUSTER_DEVICE", "0") not in ("0", "")
+
+
+@contextlib.contextmanager
+def cluster_device(enabled):
+    """CLUSTER_DEVICE set to `enabled` inside the block, restored on the way out"""
+    global CLUSTER_DEVICE
+    was = CLUSTER_DEVICE
+    CLUSTER_DEVICE = bool(enabled)
+    try:
+        yield
+    finally:
+        CLUSTER_DEVICE = was
+
+
+def cluster_samples_device(box, absd, count, threshold, output_num, H, W, out=None):
+    """apply_cluster + final ranking of build_samples' output on the device: box int32 [B,N,4], absd fp32 [B,N], count int32 [B]
+    (ranked candidates) -> (box [B,output_num,4], absd [B,output_num], count [B]) in the same format; images with at most
+    output_num candidates pass through. A threshold outside [0, 1) is refused (DenetHipError): that is the host routine's case"""
+    B, N, _ = box.shape
+    output_num = int(output_num)
+    nbytes = _L().denet_cluster_samples_workspace_bytes(B, N)
+    ws = WS.get("cluster", nbytes)
+    if out is not None:
+        obox, oabsd, ocount = out
+    else:
+        obox = torch.empty((B, max(output_num, 1), 4), dtype=torch.int32, device="cuda")
+        oabsd = empty(B, max(output_num, 1))
+        ocount = torch.empty((B,), dtype=torch.int32, device="cuda")
+    check(_L().denet_cluster_samples_device(ptr(box), ptr(absd), ptr(count), B, N, float(threshold), output_num, int(H), int(W),
+                                            ptr(obox), ptr(oabsd), ptr(ocount), ptr(ws), ws.numel(), stream_ptr()),
+          "cluster_samples_device")
+    if PROFILE is not None:
+        for _ in range(4):                 # (the records of the four cluster_* launches)
+            PROFILE.add(0.0)
+    return obox, oabsd, ocount
 
 
 def detect_decode(logits, roi_bbox, class_num, jointfit, nreg, overlap_threshold, nfit=0):

@@ -47,6 +47,7 @@ SWITCHES = {
     "DENET_WGRAD_STREAM": ("1", "kernels", "the filter-gradient chain of the backward sweep on a second stream"),
     "DENET_SHORT_HANDOFF": ("1", "host", "the short forms of the RoI hand-off (device-side editing / one native call)"),
     "DENET_HANDOFF_WARM_MS": ("0.25", "host", "milliseconds between dry runs of the hand-off's native call while the host waits for the proposal (0: none)"),
+    "DENET_CLUSTER_DEVICE": ("0", "kernels", "OPT-IN, never the headline: DNS layers with 0 <= nmsThreshold < 1 cluster their 10 * sn^2 candidates on the device (csrc/cluster.hip, ops.CLUSTER_DEVICE, --device-cluster) and take the short forms of the RoI hand-off; ties of the fp32 score are broken by rank instead of the host routine's member order"),
     "DENET_SIDE_SORT": ("1", "kernels", "the gather gradient's tap sort queued right behind the forward gather"),
     "DENET_SORT_ONE_KERNEL": ("1", "kernels", "the tap sort as one 1024-thread workgroup per image"),
     "DENET_SOFT_NMS_HOST": ("unset", "host", "inference: force the host (1) / device (0) form of Gaussian soft-NMS"),

@@ -701,6 +701,20 @@ int denet_host_cluster_samples(const float* samples_host, int n, float threshold
                                int* out_count);
 int denet_samples_finish_host(const int* box_host, const float* absd_host, const int* count_host, int B,
                               int sample_count, int H, int W, float* samples_host);
+/* apply_cluster + the final ranking ON THE DEVICE (opt-in: ops.CLUSTER_DEVICE / DENET_CLUSTER_DEVICE), for 0 <= threshold < 1, by
+ * the closed form of csrc/cluster.hip: connected components of the graph "fp32 overlap_iou > threshold", a component ordered by
+ * its youngest creator, cut to output_num components by (size descending, creation order), 1 + floor(size * ratio) best members
+ * each, ranked, cut to output_num. Input box_in [B][N][4] int32, absd_in [B][N], count_in [B] and output box_out
+ * [B][output_num][4], absd_out [B][output_num], count_out [B] are in denet_build_samples' format (device memory); H x W the corner
+ * map. An image with count <= output_num is copied through. Ties of the fp32 score are broken by rank (position in the input
+ * list); on tie-free lists the result equals denet_host_cluster_samples' on the finished rows, row for row. Refused with a
+ * message, never computed: threshold outside [0, 1), output_num <= 0, a workspace smaller than
+ * denet_cluster_samples_workspace_bytes(B, N). Launches: cluster_init_kernel, cluster_pairs_kernel, cluster_label_kernel,
+ * cluster_select_kernel. */
+size_t denet_cluster_samples_workspace_bytes(int B, int N);
+int denet_cluster_samples_device(const int* box_in, const float* absd_in, const int* count_in, int B, int N, float threshold,
+                                 int output_num, int H, int W, int* box_out, float* absd_out, int* count_out, void* workspace,
+                                 size_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
