@@ -568,6 +568,18 @@ extern "C" int denet_bn_fwd_train_pre(const float* x, const float* res, float* y
     return DENET_OK;
 }
 
+// the first stage of the statistics alone: workspace (denet_bn_workspace_bytes) <- partial [*rows][2][C] doubles, the rows
+// denet_bn_fwd_train reduces (same kernel, same grid); for a consumer that finishes them itself (csrc/bn_renorm.hip)
+extern "C" int denet_bn_stats_partial(const float* x, void* workspace, int* rows, long M, int C, hipStream_t stream) {
+    DENET_CHECK_ARG(x && workspace && rows, "bn_stats_partial: null pointer");
+    DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_stats_partial: bad shape M=%ld C=%d", M, C);
+    BnMap m = bn_map(M, C);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, M, C, m.LC, (double*)workspace);
+    DENET_CHECK_LAUNCH("bn_stats_partial");
+    *rows = m.gy;
+    return DENET_OK;
+}
+
 extern "C" int denet_bn_stats_final(const double* partial, int rows, long M, int C, float momentum, float eps, float* run_mean,
                                     float* run_stdinv, float* save_mean, float* save_invstd, hipStream_t stream) {
     DENET_CHECK_ARG(partial && rows > 0 && save_mean && save_invstd && M > 0 && C > 0, "bn_stats_final: bad arguments");

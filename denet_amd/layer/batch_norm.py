@@ -1,11 +1,60 @@
 """`BN` layer — spatial batch normalisation. Mirrors denet/layer/batch_norm.py (BatchNormLayer :12-129):
 cuDNN batch statistics (biased variance, eps inside the sqrt), running `mean` and running INVERSE standard
 deviation `stdinv` with momentum (:75-76), gamma/beta reported as biases (no L2 decay, :106-107), and the
-test-time path that feeds var = 1/stdinv^2 to cuDNN which adds eps a second time (:50-52)."""
+test-time path that feeds var = 1/stdinv^2 to cuDNN which adds eps a second time (:50-52).
+The batch renormalisation the reference keeps commented out (:65-73) runs here for the layers whose parameters ask for it
+(renormMaxR > 1 or renormMaxD > 0): ops.bn_renorm_fwd_train / bn_renorm_bwd, DESIGN.md section 14."""
+import math
+
 import numpy
 
-from . import AbstractLayer, Act, Param, get_train
+from . import AbstractLayer, Act, Param, get_epoch, get_train
 from .. import ops
+
+
+def renorm_active(max_r, max_d):
+    """batch renormalisation is asked for (the condition of the reference's commented-out block, batch_norm.py:66)"""
+    return max_r > 1.0 or max_d > 0.0
+
+
+def renorm_check(max_r, max_d, max_it):
+    """refuses limits no step could run with, when the layer is built"""
+    for name, v in (("renormMaxR", max_r), ("renormMaxD", max_d), ("renormMaxIt", max_it)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, numpy.integer, numpy.floating)) or not math.isfinite(v):
+            raise ValueError("batch norm: %s must be a finite number, got %r" % (name, v))
+    if max_r < 1.0:
+        raise ValueError("batch norm: renormMaxR must be >= 1 (1 = no correction of the scale), got %r" % (max_r,))
+    if max_d < 0.0:
+        raise ValueError("batch norm: renormMaxD must be >= 0 (0 = no correction of the mean), got %r" % (max_d,))
+    if max_it < 0:
+        raise ValueError("batch norm: renormMaxIt must be >= 0 (epochs over which the limits open; 0 = open from the start), "
+                         "got %r" % (max_it,))
+
+
+def renorm_limits(max_r, max_d, max_it, epoch):
+    """(r_max, d_max) of a training step in `epoch` (batch_norm.py:67-70): the limits open from (1, 0) at epoch 0 to (max_r, max_d)
+    at epoch max_it. The reference divides by max_it; the `BN[...]` grammar defaults it to 0, which means no ramp here"""
+    if max_it <= 0:
+        return float(max_r), float(max_d)
+    r_max = min(float(max_r), math.exp(epoch * math.log(max_r) / max_it))
+    d_max = min(float(max_d), math.exp(epoch * math.log(max_d + 1.0) / max_it) - 1.0)
+    return max(r_max, 1.0), max(d_max, 0.0)
+
+
+def renorm_layers(model):
+    """the renorm-active batch norms of a model, nested ones included"""
+    from ..model.model_cnn import walk_layers
+    return [l for l in walk_layers(model.layers) if isinstance(l, BatchNormLayer) and l.enabled and l.renorm_active]
+
+
+def renorm_log_line(model, epoch):
+    """what model-train reports at the start of an epoch, or None for a model without renorm-active layers"""
+    ls = renorm_layers(model)
+    if not ls:
+        return None
+    lims = sorted({renorm_limits(l.renorm_max_r, l.renorm_max_d, l.renorm_max_it, epoch) for l in ls})
+    return "batch renorm: %d active layers, epoch %d limits %s" % (
+        len(ls), epoch, " ".join("r_max=%.6g d_max=%.6g" % lim for lim in lims))
 
 
 class BatchNormLayer(AbstractLayer):
@@ -23,6 +72,9 @@ class BatchNormLayer(AbstractLayer):
         self.renorm_max_d = json_param.get("renormMaxD", renorm_max_d)
         self.renorm_max_it = json_param.get("renormMaxIt", renorm_max_it)
         self.eps = json_param.get("eps", eps)
+        renorm_check(self.renorm_max_r, self.renorm_max_d, self.renorm_max_it)
+        # renorm-active layers take a route of their own in training (csrc/bn_renorm.hip) and give up every fusion
+        self.renorm_active = renorm_active(self.renorm_max_r, self.renorm_max_d)
         self.output_shape = self.input_shape
         if self.enabled:
             assert self.input.cp == self.input_shape[1], "batch norm needs an unpadded channel count (multiple of 32)"
@@ -83,7 +135,7 @@ class BatchNormLayer(AbstractLayer):
     def stats_final(self, act):
         """for the convolution pass that writes `act` (this layer's input) in a training step: the description of this layer's
         statistics, so that the pass can finish them in its own launch (ops.BnFinal; the running statistics are updated there)"""
-        if not (self.enabled and ops.FINAL_FOLD and act is self.input):
+        if not (self.enabled and ops.FINAL_FOLD and act is self.input) or self.renorm_active:
             return None
         if getattr(self, "pool_behind", None) is not None and ops.BN_POOL_FUSE:
             # the fused BN + ReLU + max-pool pass reduces the partial rows itself and updates the running statistics there
@@ -110,6 +162,17 @@ class BatchNormLayer(AbstractLayer):
             # per-channel sums already written by the convolution that produced x (ConvLayer.forward), valid for this tensor only
             pre = getattr(self.input, "stats", None)
             self.input.stats = None
+            if self.renorm_active:
+                # batch renormalisation (batch_norm.py:65-73): the producer's sums or the layer's own, finished together with r, d
+                # and the running statistics in one launch; the pointwise pass runs at once (no BnLink, no pool fusion)
+                r_max, d_max = renorm_limits(self.renorm_max_r, self.renorm_max_d, self.renorm_max_it, get_epoch())
+                y, sm, si, state = ops.bn_renorm_fwd_train(x, self.omega.dev, self.beta.dev, self.mean.dev, self.stdinv.dev, r_max,
+                                                           d_max, self.momentum, self.eps, relu=relu, res=res, pre=pre)
+                self._save = (sm, si, relu, out_act, res is not None)
+                self._renorm_state = state
+                self._pooled = False
+                out_act.data = y
+                return
             pool = getattr(self, "pool_behind", None)
             own_out = self.act_behind.output if getattr(self, "act_fused", False) else self.output
             if pool is not None and ctx is not None and relu and res is None and out_act is own_out and ops.BN_POOL_FUSE:
@@ -156,7 +219,7 @@ class BatchNormLayer(AbstractLayer):
     def sums_request(self, act):
         """for the data-gradient pass that writes the gradient of `act` (this layer's output of the current training step): the
         description of this batch norm, so that the pass leaves the two backward reductions behind (ops.BnSums)"""
-        if not (self.enabled and self._save is not None):
+        if not (self.enabled and self._save is not None) or self.renorm_active:
             return None
         if getattr(self, "_pooled", False):
             # the fused BN + ReLU + max pool: `act` is the POOL's output; over the pooled tensors the layer looks like a batch norm
@@ -181,6 +244,12 @@ class BatchNormLayer(AbstractLayer):
         if not self.enabled:
             return None
         sm, si, relu, out_act, has_res = self._save
+        if self.renorm_active:
+            y = out_act.data if (relu and has_res) else None      # (no residual: the mask is recomputed from x, as in the forward)
+            dx, dres, _, _ = ops.bn_renorm_bwd(self.input.data, y, out_act.grad, sm, si, self._renorm_state, relu=relu,
+                                               want_dres=want_dres, dgamma=self.omega.grad, dbeta=self.beta.grad)
+            self.input.add_grad(dx)
+            return dres
         if getattr(self, "_pooled", False):
             pool = self.pool_behind
             k, s, p = pool.size[0], pool.stride[0], pool.pad[0]

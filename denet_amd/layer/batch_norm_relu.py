@@ -38,4 +38,8 @@ class BatchNormReluLayer(BatchNormLayer):
                      "std": self.stdinv.get_value(),
                      "gamma": self.omega.get_value(),
                      "bias": self.beta.get_value()})
+        if self.renorm_active:
+            # the reference's fused layer has no such keys (:85-167); they are read from JSON / a residual block's bnParam
+            # (BatchNormLayer.__init__) and written only when they switch batch renormalisation on: default files keep their bytes
+            json.update({"renormMaxR": self.renorm_max_r, "renormMaxD": self.renorm_max_d, "renormMaxIt": self.renorm_max_it})
         return json

@@ -98,6 +98,10 @@ SIGNATURES = {
     "denet_bn_relu_pool_bwd_apply": (I, [P] * 9 + [I] * 9 + [P]),
     "denet_bn_fold": (I, [P] * 6 + [F, P, P, I, L, P]),
     "denet_bn_stats_final": (I, [P, I, L, I, F, F, P, P, P, P, P]),
+    "denet_bn_stats_partial": (I, [P, P, P, L, I, P]),
+    "denet_bn_renorm_workspace_bytes": (Z, [L, I]),
+    "denet_bn_renorm_fwd_train": (I, [P] * 11 + [I, P, L, I, F, F, F, F, I, P]),
+    "denet_bn_renorm_bwd": (I, [P] * 11 + [L, I, I, P]),
     "denet_bn_apply": (I, [P] * 7 + [L, I, I, P]),
     "denet_bn_bwd_sums": (I, [P] * 11 + [L, I, I, P]),
     "denet_bn_bwd_apply": (I, [P] * 10 + [L, I, I, P]),

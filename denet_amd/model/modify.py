@@ -1,7 +1,8 @@
 """Model surgery — the operations of denet/model/modify.py (:37-193) that assemble a DeNet detector from a
 classifier: --class-num, --image-size, --use-cudnn-pool (:62-68), --convert-bn-relu (:76-113), --modify-bn (:115-131), --layer-remove
 (:153-156), --layer-insert N:DESC (:161-175), --layer-append (:177-184). Like the reference every edit goes
-through the JSON form and a reload, so shapes and wiring are rebuilt from scratch."""
+through the JSON form and a reload, so shapes and wiring are rebuilt from scratch. --modify-bn-renorm R D IT is this build's
+own: the switch for the batch renormalisation the reference carries parameters for and keeps commented out (batch_norm.py:65-73)."""
 import copy
 
 from . import model_cnn
@@ -43,7 +44,47 @@ def _bn_to_bnrelu(bn_json):
     out = {"type": "batchnorm-relu", "layers": []}
     for k in ("momentum", "eps", "mean", "std", "gamma", "bias"):
         out[k] = bn_json[k]
+    if bn_json.get("renormMaxR", 1.0) > 1.0 or bn_json.get("renormMaxD", 0.0) > 0.0:
+        for k in RENORM_KEYS:          # a renorm-active layer stays one (the fused layer writes the keys only then)
+            if k in bn_json:
+                out[k] = bn_json[k]
     return out
+
+
+RENORM_KEYS = ("renormMaxR", "renormMaxD", "renormMaxIt")
+
+
+def modify_bn_renorm(model, max_r, max_d, max_it):
+    """--modify-bn-renorm R D IT: the batch-renormalisation limits (the reference's commented-out block, denet/layer/batch_norm.py:
+    65-73) of every batchnorm and batchnorm-relu layer and of the bnParam of every residual block; modify_bn's traversal.
+    R = 1, D = 0 switches it off again: the keys leave every place that does not carry them by default. A top-level `batchnorm`
+    always exports the three keys, so it gets the values as given: after `1 0 0` its renormMaxIt reads 0 (the grammar's default),
+    also where the file carried the constructor's 10 before, as older and reference files do - the value has no effect on a
+    layer that is switched off"""
+    from ..layer.batch_norm import renorm_active, renorm_check
+    renorm_check(max_r, max_d, max_it)
+    max_r, max_d, max_it = float(max_r), float(max_d), int(max_it) if float(max_it).is_integer() else float(max_it)
+    upd = {"renormMaxR": max_r, "renormMaxD": max_d, "renormMaxIt": max_it}
+    active = renorm_active(max_r, max_d)
+
+    def edit(d, always):
+        if active or always:
+            d.update(upd)
+        else:
+            for k in RENORM_KEYS:
+                d.pop(k, None)
+
+    j = model.export_json()
+    for l in j["layers"]:
+        if l["type"] in ("batchnorm", "batchnorm-relu"):
+            edit(l, l["type"] == "batchnorm")
+        elif l["type"] == "resnet":
+            l["bnParam"] = dict(l.get("bnParam", {}))
+            edit(l["bnParam"], False)
+            for s in l["layers"]:
+                if s["type"] in ("batchnorm", "batchnorm-relu"):
+                    edit(s, False)
+    return _reload(model, j)
 
 
 def convert_bn_relu(model):
@@ -200,6 +241,10 @@ def build_parser():
     parser.add_argument("--convert-bn-relu", default=False, action="store_true")
     parser.add_argument("--merge", default=False, action="store_true", help="merge split layers")
     parser.add_argument("--modify-bn", default=None, nargs="+", type=str, help="enabled momentum eps for batch norm")
+    parser.add_argument("--modify-bn-renorm", default=None, nargs=3, type=float, metavar=("R", "D", "IT"),
+                        help="batch renormalisation for every batch norm (training only): r is clipped to [1/R, R], d to [-D, D], the "
+                             "limits open over the first IT epochs (0: open from the start); 1 0 0 switches it off (a top-level batchnorm "
+                             "layer then carries renormMaxIt 0, whatever it carried before)")
     parser.add_argument("--modify-layer", default=None, nargs="+", type=str, help="TYPE key=value ...")
     parser.add_argument("--layer-insert", default=[], nargs="+", help="insert layer at position N:DESC")
     parser.add_argument("--layer-remove", default=0, type=int, help="remove N layer from end")
@@ -225,6 +270,8 @@ def main(argv=None):
         model = use_cudnn_pool(model)
     if args.modify_bn is not None:
         model = modify_bn(model, bool(args.modify_bn[0]), float(args.modify_bn[1]), float(args.modify_bn[2]))
+    if args.modify_bn_renorm is not None:
+        model = modify_bn_renorm(model, *args.modify_bn_renorm)
     if args.convert_bn_relu:
         model = convert_bn_relu(model)
     model = layer_remove(model, args.layer_remove)

@@ -178,7 +178,11 @@ def train(args, train_data, log=None, test_data=None):
         from ..dataset.device_render import DeviceImageLoader
         device_loader = DeviceImageLoader(max(1, getattr(args, "thread_num", 1)), True, cp=model.input.cp, decode="process",
                                           params=train_data.image_loader)
+    from ..layer.batch_norm import renorm_log_line
     for epoch in range(args.epochs):
+        renorm = None if skip_train else renorm_log_line(model, epoch)
+        if renorm is not None:
+            log(renorm)                  # renorm-active batch norms (BN[m, eps, r, d, it]): this epoch's r_max / d_max
         if not skip_train:
             train_data.shuffle()
         for subset in range(0 if skip_train else train_data.subset_num):

@@ -87,7 +87,11 @@ def train(args, train_data, dp, log=None):
     for epoch in range(0, epoch_start):                 # train_multi.py:406-410
         if len(args.learn_anneal_epochs) == 0 or (epoch + 1) in args.learn_anneal_epochs:
             learn_rate *= args.learn_anneal
+    from ..layer.batch_norm import renorm_log_line
     for epoch in range(epoch_start, args.epochs):
+        renorm = renorm_log_line(model, epoch) if rank == 0 else None
+        if renorm is not None:
+            log(renorm + " (per GPU: the correction needs no communication)")
         random.seed(args.seed + epoch)                 # same order on every rank (train_multi.py:44-46)
         train_data.shuffle()
         # a restarted run continues the first epoch behind the subsets the checkpoint has seen (UpdateClient(epoch_start,

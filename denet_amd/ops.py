@@ -59,7 +59,7 @@ def kernel_symbol(kind, a, b, c):
         return "conv_bf16_wgrad_kernel<%d, %d>" % (a, b)       # tile BM x BN of the opt-in bf16 filter gradient
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
              24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
-             33: "cluster_select_kernel"}.get(kind)
+             33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
 
@@ -1822,6 +1822,49 @@ def bn_bwd(x, y, dy, gamma, save_mean, save_invstd, relu=False, want_dres=False,
     dbeta = dbeta if dbeta is not None else empty(C)
     check(_L().denet_bn_bwd(ptr(x), ptr(y), ptr(dy), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), ptr(dx), ptr(dres),
                             ptr(dgamma), ptr(dbeta), ptr(_bn_ws(M, C)), M, C, int(relu), stream_ptr()), "bn_bwd")
+    return dx, dres, dgamma, dbeta
+
+
+# ---- batch renormalisation (csrc/bn_renorm.hip; the commented-out block denet/layer/batch_norm.py:65-73) ----
+RENORM_KERNELS = ("bn_renorm_stats_finish_kernel", "bn_renorm_grad_fold_kernel")      # what a renorm-active layer adds to a step
+
+
+def bn_renorm_fwd_train(x, gamma, beta, run_mean, run_stdinv, r_max, d_max, momentum=0.9, eps=1e-5, relu=False, res=None, out=None,
+                        pre=None):
+    """bn_fwd_train for a renorm-active layer: y = (x - mu_b) * gamma * inv_b * r + beta + gamma * d [+ res] [relu], r / d clipped
+    to this step's limits against the running statistics of BEFORE the call, which are then updated in the same launch. pre =
+    (partial sums, rows) of the producing convolution, or None: measured here. Returns (y, save_mean, save_invstd, state) with
+    state [4][C] = r | d | gamma * r | beta + gamma * d, which bn_renorm_bwd takes"""
+    C = x.shape[-1]
+    M = x.numel() // C
+    assert pre is None or len(pre) == 2, "statistics finished by the producer in front of a renorm-active batch norm"
+    y = out if out is not None else torch.empty_like(x)
+    save_mean, save_invstd, state = empty(C), empty(C), empty(4, C)
+    ws = WS.get("bn", _L().denet_bn_renorm_workspace_bytes(M, C)) if pre is None else None
+    check(_L().denet_bn_renorm_fwd_train(ptr(x), ptr(res), ptr(y), ptr(gamma), ptr(beta), ptr(run_mean), ptr(run_stdinv),
+                                         ptr(save_mean), ptr(save_invstd), ptr(state), ptr(pre[0]) if pre is not None else None,
+                                         int(pre[1]) if pre is not None else 0, ptr(ws), M, C, float(momentum), float(eps),
+                                         float(r_max), float(d_max), int(relu), stream_ptr()), "bn_renorm_fwd_train")
+    if PROFILE is not None:
+        PROFILE.add(0.0)                   # (the record of the statistics-finish launch)
+    return y, save_mean, save_invstd, state
+
+
+def bn_renorm_bwd(x, y, dy, save_mean, save_invstd, state, relu=False, want_dres=False, dgamma=None, dbeta=None, dx=None):
+    """gradient of bn_renorm_fwd_train (r and d are constants): dgamma = r * s2 + d * s1, dbeta = s1, dx = gamma * inv_b * r * (g -
+    s1 / M - xhat * s2 / M), dres = g. y: the forward output when a residual was added under a ReLU, else None (the mask is
+    recomputed from x). Returns (dx, dres, dgamma, dbeta)"""
+    C = x.shape[-1]
+    M = x.numel() // C
+    dx = dx if dx is not None else torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    dgamma = dgamma if dgamma is not None else empty(C)
+    dbeta = dbeta if dbeta is not None else empty(C)
+    ws = WS.get("bn", _L().denet_bn_renorm_workspace_bytes(M, C))
+    check(_L().denet_bn_renorm_bwd(ptr(x), ptr(y), ptr(dy), ptr(save_mean), ptr(save_invstd), ptr(state), ptr(dx), ptr(dres),
+                                   ptr(dgamma), ptr(dbeta), ptr(ws), M, C, int(relu), stream_ptr()), "bn_renorm_bwd")
+    if PROFILE is not None:
+        PROFILE.add(0.0)                   # (the record of the gradient-fold launch)
     return dx, dres, dgamma, dbeta
 
 

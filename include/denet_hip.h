@@ -460,6 +460,31 @@ int denet_bn_fold(const float* w, const float* conv_bias, const float* gamma, co
 int denet_bn_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* beta,
                  const float* save_mean, const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta,
                  void* workspace, long M, int C, int relu, hipStream_t stream);
+/* the first stage of denet_bn_fwd_train's statistics alone: workspace (denet_bn_workspace_bytes) <- partial [*rows][2][C] doubles
+ * (sum | sum of squares over disjoint row sets; batch_norm.py:50-53), for a caller that finishes them itself */
+int denet_bn_stats_partial(const float* x, void* workspace, int* rows, long M, int C, hipStream_t stream);
+/* Batch renormalisation, training (the commented-out block denet/layer/batch_norm.py:65-73; csrc/bn_renorm.hip, DESIGN.md
+ * section 14). Per channel, against the running statistics as they stand BEFORE this call's update:
+ *   r = clip((1 / inv_b) * stdinv, 1 / r_max, r_max), d = clip((mu_b - mean) * stdinv, -d_max, d_max)       (no gradient, :71-72)
+ *   y = (x - mu_b) * (gamma * inv_b * r) + (beta + gamma * d) [+ res] [relu]                                  (:73)
+ * r_max >= 1, d_max >= 0: this step's limits (:66-70; the caller evaluates the ramp over the epoch).
+ *   fwd_train: statistics from partial / rows (a producing convolution's sums, as denet_bn_fwd_train_pre) or, partial = NULL, measured
+ *              here (workspace: denet_bn_renorm_workspace_bytes). ONE launch (bn_renorm_stats_finish_kernel) reduces the rows in
+ *              denet_bn_stats_final's order (no atomics, bitwise reproducible; save_mean / save_invstd are bit-identical to its),
+ *              writes state [4][C] = r | d | gamma * r | beta + gamma * d and then updates run_mean / run_stdinv (:75-76); the
+ *              pointwise pass is denet_bn_apply on the effective vectors.
+ *   bwd:       denet_bn_bwd_sums + denet_bn_bwd_apply on the same effective vectors (y = NULL: the ReLU mask is recomputed from x,
+ *              exactly the forward's); between them bn_renorm_grad_fold_kernel writes dgamma = r * s2 + d * s1, dbeta = s1
+ *              (s1 = sum g, s2 = sum g * xhat, held in the workspace - dgamma never holds s2). dx = gamma * inv_b * r * (g - s1 / M
+ *              - xhat * s2 / M), dres (optional) = g. */
+size_t denet_bn_renorm_workspace_bytes(long M, int C);
+int denet_bn_renorm_fwd_train(const float* x, const float* res, float* y, const float* gamma, const float* beta, float* run_mean,
+                              float* run_stdinv, float* save_mean, float* save_invstd, float* state, const double* partial, int rows,
+                              void* workspace, long M, int C, float momentum, float eps, float r_max, float d_max, int relu,
+                              hipStream_t stream);
+int denet_bn_renorm_bwd(const float* x, const float* y, const float* dy, const float* save_mean, const float* save_invstd,
+                        const float* state, float* dx, float* dres, float* dgamma, float* dbeta, void* workspace, long M, int C,
+                        int relu, hipStream_t stream);
 /* A max pool directly behind a BN + ReLU layer (batch_norm_relu.py:34-48 -> pool.py:38, the ResNet stem), training: the
  * normalised tensor is never written. Forward: statistics from `partial` / `rows` (denet_conv_fwd_stats) or, partial = NULL,
  * measured here (workspace = denet_bn_workspace_bytes(N*H*W, C)); writes y_pool [N,OH,OW,C] and the argmax taps (first maximum
