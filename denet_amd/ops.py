@@ -745,6 +745,11 @@ def static_policy(mode, g):
     return 0
 
 
+def direct_policy(mode, g):
+    """the direct kernel for every pass: no Winograd or fused algorithm, nothing measured"""
+    return 0
+
+
 def _decided(mode, g):
     """the implementation fixed for this pass (0 direct, 2 / 4 Winograd tile, FUSED2), None while undecided"""
     _load_tuned_once()
@@ -754,6 +759,53 @@ def _decided(mode, g):
         if policy is not None:
             use = _WINO[(mode, g)] = int(policy(mode, g))
     return use
+
+
+# module globals whose value also lives on the C side: name -> the setter that keeps the two together
+_C_SIDE = {"FINAL_FOLD": "set_final_fold"}
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """each named module global of ops set to the given value inside the block, and what it held before put back on the way out
+    (exceptions included). Only an existing plain global is taken - data, not a function, class or module - and one whose value
+    the C side holds too is refused with the name of its setter: a bad name raises before anything is changed"""
+    g = globals()
+    for name in values:
+        if name in _C_SIDE:
+            raise ValueError("ops.%s also lives on the C side: set it through ops.%s" % (name, _C_SIDE[name]))
+        # (a function, class or module is a global that carries its own name; POLICY may hold a function, under another name)
+        if name not in g or isinstance(g[name], type(os)) or getattr(g[name], "__name__", None) == name:
+            raise AttributeError("ops.%s is not a switch (an existing module global that holds data)" % name)
+    was = {name: g[name] for name in values}
+    g.update(values)
+    try:
+        yield
+    finally:
+        g.update(was)
+
+
+@contextlib.contextmanager
+def algorithms(table=None, **values):
+    """the algorithm tables as a block: POLICY, _WINO and _TUNED are on the way out what they were on entry (the committed tuned
+    file is loaded first, so a snapshot never misses it), and decisions made inside are dropped. table: the contents _WINO starts
+    the block with (the dict object stays the same one); values: switches() for the block, e.g. POLICY=static_policy, POLICY=None,
+    AUTOTUNE=True, DGRAD_T=False. Yields the live _WINO, to add or remove entries in mid-block. Nests. Under DENET_TUNE=1 a
+    geometry measured inside a block is forgotten with the block: it may be measured again later"""
+    _load_tuned_once()
+    wino, tuned = dict(_WINO), set(_TUNED)
+    values.setdefault("POLICY", POLICY)
+    try:
+        with switches(**values):
+            if table is not None:
+                _WINO.clear()
+                _WINO.update(table)
+            yield _WINO
+    finally:
+        _WINO.clear()
+        _WINO.update(wino)
+        _TUNED.clear()
+        _TUNED.update(tuned)
 
 
 def _tile_allowed(mode, tile):
@@ -1617,17 +1669,10 @@ def bump_weights_version():
 INFER_FOLD = os.environ.get("DENET_INFER_FOLD", "1") != "0"      # inference: batch norm folded into the convolution in front
 
 
-@contextlib.contextmanager
 def infer_fold(enabled):
     """INFER_FOLD set to `enabled` inside the block, restored on the way out (model/update_bn.py: a batch norm folded into the
     convolution in front never runs its own forward, and its input holds normalised values)"""
-    global INFER_FOLD
-    was = INFER_FOLD
-    INFER_FOLD = bool(enabled)
-    try:
-        yield
-    finally:
-        INFER_FOLD = was
+    return switches(INFER_FOLD=bool(enabled))
 
 
 # OPT-IN, never the headline (bench.py never sets it): inference convolutions with both operands rounded to bf16 on the bf16
@@ -1644,15 +1689,9 @@ def _precision(what, name):
     return name
 
 
-@contextlib.contextmanager
 def _precision_block(var, what, name):
     """the module global `var` (INFER_PRECISION / TRAIN_PRECISION) set to `name` inside the block, restored on the way out"""
-    was = globals()[var]
-    globals()[var] = _precision(what, name)
-    try:
-        yield
-    finally:
-        globals()[var] = was
+    return switches(**{var: _precision(what, name)})
 
 
 def infer_precision(name):
@@ -2366,16 +2405,9 @@ def cluster_samples_host(raw, counts, threshold, output_num):
 CLUSTER_DEVICE = os.environ.get("DENET_CLUSTER_DEVICE", "0") not in ("0", "")
 
 
-@contextlib.contextmanager
 def cluster_device(enabled):
     """CLUSTER_DEVICE set to `enabled` inside the block, restored on the way out"""
-    global CLUSTER_DEVICE
-    was = CLUSTER_DEVICE
-    CLUSTER_DEVICE = bool(enabled)
-    try:
-        yield
-    finally:
-        CLUSTER_DEVICE = was
+    return switches(CLUSTER_DEVICE=bool(enabled))
 
 
 def cluster_samples_device(box, absd, count, threshold, output_num, H, W, out=None):

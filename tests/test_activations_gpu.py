@@ -14,10 +14,11 @@ import subprocess
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 from denet_amd import ops
 from denet_amd.model import model_cnn, zoo
+from fp64_model import act64 as _act64, build_model, param_layers as _param_layers, png_dataset as _png_dataset, reference as _reference
+from fp64_model import rel as _rel, sgd_step_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -29,35 +30,8 @@ KINDS = ["sigmoid", "tanh", "elu", "softplus"]
 def _algorithm_tables_restored():
     """ops memoises per geometry which implementation a convolution pass takes (ops._WINO); the small geometries of this file
     are those of other files' tests, which must find the tables as a fresh process has them"""
-    ops._load_tuned_once()
-    saved = (ops.POLICY, dict(ops._WINO), set(ops._TUNED))
-    yield
-    ops.POLICY = saved[0]
-    ops._WINO.clear()
-    ops._WINO.update(saved[1])
-    ops._TUNED.clear()
-    ops._TUNED.update(saved[2])
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max())
-
-
-def _act64(name, x):
-    """the table of the issue, in the dtype of x (float64 here): denet/layer/activation.py:25-44"""
-    if name == "sigmoid":
-        return torch.sigmoid(x)
-    if name == "tanh":
-        return torch.tanh(x)
-    if name == "elu":
-        return torch.where(x > 0, x, torch.expm1(x))
-    if name == "softplus":
-        return torch.clamp(x, min=0) + torch.log1p(torch.exp(-x.abs()))
-    if name in ("relu", "relu-safe"):
-        return torch.relu(x)
-    assert name == "none", name
-    return x
+    with ops.algorithms():
+        yield
 
 
 def _dact64(name, x):
@@ -156,106 +130,9 @@ def test_kernels_vs_fp64(hip, kind, C):
 NET_DESC = "C.B[32,3] A C[32,3] BN A P[2] nRSN.O[2,64,3,2] nRSN[2,64,3,2,32] R.C"
 
 
-def _build(desc, activation, B, size, class_num=10, seed=5, border="half"):
-    np.random.seed(seed)
-    m = model_cnn.ModelCNN()
-    m.batch_size = B
-    m.class_num = class_num
-    m.build(desc, (3, size, size), activation, border, ["he-backward"])
-    # batch norms away from (gamma, beta) = (1, 0): both gradients carry weight
-    rng = np.random.RandomState(seed + 1)
-    for l in model_cnn.walk_layers(m.layers):
-        if l.type_name == "batchnorm" and l.enabled:
-            l.omega.set_value(rng.uniform(0.7, 1.3, l.omega.value.shape))
-            l.beta.set_value(rng.normal(0.0, 0.3, l.beta.value.shape))
-    if m.layers[-1].type_name == "regression":
-        # logits of order one: with the initialisation as it is they reach the hundreds on these nets, the soft-max saturates (the
-        # test-mode probabilities come out as exact zeros and ones) and the comparison of the probabilities says nothing
-        head = m.layers[-2]
-        head.omega.set_value(head.omega.get_value() * 0.05)
-    return m
-
-
-def _param_layers(model):
-    out = []
-    for l in model_cnn.walk_layers(model.layers):
-        if l.type_name == "conv":
-            out.append((l, [l.omega] + ([l.beta] if l.use_bias else [])))
-        elif l.type_name == "batchnorm" and l.enabled:
-            out.append((l, [l.omega, l.beta]))
-    return out
-
-
-def _reference(model, x, params, cls, train, running=None):
-    """the layer list in float64 on the host, wired like the layers themselves: every layer reads the tensor of its `input` handle
-    and writes the one of its `output` handle. Returns (cost, logits, {id(batch norm): (mean, stdinv) of the batch})."""
-    val = {id(model.layers[0].output): torch.from_numpy(x).double()}
-    stats = {}
-
-    def run(l):
-        t = l.type_name
-        if t == "initial":
-            return
-        h = val[id(l.input)]
-        if t == "conv":
-            ps = params[id(l)]
-            h = Fn.conv2d(h, ps[0].flip(2, 3), stride=l.stride[0], padding=l.pad)      # (true convolution: convolution.py:80-83)
-            if l.use_bias:
-                h = h + ps[1][None, :, None, None]
-        elif t == "batchnorm":
-            if not l.enabled:
-                return
-            gamma, beta = params[id(l)]
-            if train:
-                mean = h.mean(dim=(0, 2, 3))
-                var = h.var(dim=(0, 2, 3), unbiased=False)
-                stats[id(l)] = (mean.detach(), 1.0 / torch.sqrt(var.detach() + l.eps))
-                h = (h - mean[None, :, None, None]) / torch.sqrt(var + l.eps)[None, :, None, None]
-            else:
-                rm, rs = running[id(l)]
-                inv = 1.0 / torch.sqrt((1.0 / rs) ** 2 + l.eps)                         # batch_norm.py:50-52: eps twice
-                h = (h - rm[None, :, None, None]) * inv[None, :, None, None]
-            h = h * gamma[None, :, None, None] + beta[None, :, None, None]
-        elif t == "activation":
-            h = _act64(l.activation, h)
-        elif t == "pool":
-            assert l.mode == "max"
-            h = Fn.max_pool2d(h, l.size[0], l.stride[0], l.pad[0])
-        elif t == "resnet":
-            for s in l.layers:
-                run(s)
-            y = val[id(l.layers[l.n_main - 1].output)]
-            sc = l.layers[l.n_main:]
-            xs = val[id(sc[-1].output)] if sc else h
-            h = xs + y if "pre-activation" in l.version else _act64(l.activation, xs + y)      # resnet.py:109-113
-        elif t == "regression":
-            yc, xc = l.valid[0][1], l.valid[0][2]
-            logits = h[:, :, yc, xc]
-            lp = torch.log_softmax(logits, dim=1)
-            val["cost"] = -lp[torch.arange(len(cls)), torch.from_numpy(cls)].mean()
-            val["logits"] = logits
-            return
-        else:
-            raise AssertionError("unexpected layer " + t)
-        val[id(l.output)] = h
-
-    for l in model.layers:
-        run(l)
-    return val["cost"], val["logits"], stats
-
-
-class _direct_policy:
-    """every convolution pass on the direct kernels (exact fp32 FMA chains)"""
-
-    def __enter__(self):
-        self.saved = (ops.POLICY, dict(ops._WINO))
-        ops._WINO.clear()
-        ops.POLICY = lambda mode, g: 0
-
-    def __exit__(self, *a):
-        ops.POLICY = self.saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(self.saved[1])
+def _build(desc, activation, B, size, class_num=10):
+    """batch norms away from (gamma, beta) = (1, 0), logits of order one"""
+    return build_model(desc, (3, size, size), B, class_num, activation, spread_bn=True, head_scale=0.05)
 
 
 @pytest.mark.parametrize("activation", KINDS + ["relu"])
@@ -268,7 +145,7 @@ def test_training_step_vs_fp64(hip, activation):
     rounding per weight, ~6e-8 relative, over reductions of at most 1 152 terms and a dozen layers).
     relu is the control: the same harness on ground that worked before."""
     B, CLS, LR, MOM, DECAY = 4, 10, 0.1, 0.9, 0.0005
-    with _direct_policy():
+    with ops.algorithms(table={}, POLICY=ops.direct_policy):
         model = _build(NET_DESC, activation, B, 32, CLS)
         blocks = [l for l in model.layers if l.type_name == "resnet"]
         assert [b.version for b in blocks] == ["original"] * 2 + ["pre-activation"] * 2
@@ -292,19 +169,11 @@ def test_training_step_vs_fp64(hip, activation):
         cost_ref.backward()
         e_cost = abs(cost - float(cost_ref.detach())) / abs(float(cost_ref.detach()))
         report, bad = [], []
-        for n, (l, ps) in enumerate(before):
-            for p, v, t in zip(ps, values[id(l)], params[id(l)]):
-                g_dev = torch.from_numpy(p.get_grad().copy()).double()
-                g_ref = t.grad
-                assert float(g_ref.abs().max()) > 0, (n, p.name)
-                dec = DECAY if id(p) in weights else 0.0
-                v64 = torch.from_numpy(v).double()
-                p_ref = v64 - LR * (g_ref + dec * v64)                  # SGD at iteration 0 (no momentum yet), L2 decay on the weights
-                p_dev = torch.from_numpy(p.get_value().copy()).double()
-                e_g, e_p = _rel(g_dev, g_ref), _rel(p_dev - v64, p_ref - v64)
-                report.append((e_g, e_p, "%s #%d %s %s: grad %.2e, update %.2e" % (activation, n, l.type_name, p.name, e_g, e_p)))
-                if not (e_g <= 1e-3 and e_p <= 1e-3):
-                    bad.append(report[-1][2])
+        for l, p, e_g, e_p, _, g_ref in sgd_step_errors(before, values, params, weights, LR, DECAY):
+            assert float(g_ref.abs().max()) > 0, (l.layer_index, p.name)
+            report.append((e_g, e_p, "%s L%d %s %s: grad %.2e, update %.2e" % (activation, l.layer_index, l.type_name, p.name, e_g, e_p)))
+            if not (e_g <= 1e-3 and e_p <= 1e-3):
+                bad.append(report[-1][2])
         print("%s: cost %.6f (float64 %.6f, %.2e), worst gradient %.2e, worst update %.2e over %d arrays" % (
             activation, cost, float(cost_ref.detach()), e_cost, max(r[0] for r in report), max(r[1] for r in report), len(report)))
         assert e_cost <= 1e-3, (cost, float(cost_ref.detach()))
@@ -313,7 +182,8 @@ def test_training_step_vs_fp64(hip, activation):
         for l, _ in before:
             if l.type_name == "batchnorm":
                 rm, rs = torch.from_numpy(l.mean.get_value().copy()).double(), torch.from_numpy(l.stdinv.get_value().copy()).double()
-                m_ref, s_ref = (1.0 - l.momentum) * stats[id(l)][0], l.momentum + (1.0 - l.momentum) * stats[id(l)][1]
+                m_ref = (1.0 - l.momentum) * stats[id(l)]["mean"]
+                s_ref = l.momentum + (1.0 - l.momentum) * stats[id(l)]["stdinv"]
                 e_run = max(e_run, _rel(rm, m_ref), _rel(rs, s_ref))
                 running[id(l)] = (rm, rs)
         print("%s: running statistics %.2e" % (activation, e_run))
@@ -443,18 +313,6 @@ def test_padding_channels_through_a_pool(hip):
 
 
 # ------------------------------------------------------------------------------------------------- command line
-def _png_dataset(root, classes=3, per_class=4, seed=0):
-    from PIL import Image
-    rng = np.random.RandomState(seed)
-    for c in range(classes):
-        d = os.path.join(root, "class%i" % c)
-        os.makedirs(d)
-        for j in range(per_class):
-            img = rng.randint(0, 256, (32, 32, 3)).astype(np.uint8)
-            img[..., c] = 200 + 10 * (j % 5)
-            Image.fromarray(img).save(os.path.join(d, "img%i.png" % j))
-
-
 def _names(layers):
     out = []
     for l in layers:

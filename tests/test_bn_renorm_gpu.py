@@ -2,7 +2,7 @@
 renormMaxD / renormMaxIt, `model-modify --modify-bn-renorm`.
 
 The reference's implementation is the commented-out block denet/layer/batch_norm.py:65-73, so there is no reference run: the yardstick
-is a float64 restatement of the definition in this file (`_ref64`, `_reference`), with autograd for the gradients:
+is a float64 restatement of the definition (`_ref64` in this file, tests/fp64_model.py for the whole model), with autograd for the gradients:
     r = clip((1 / inv_b) * stdinv, 1 / r_max, r_max)            d = clip((mu_b - mean) * stdinv, -d_max, d_max)       (constants)
     y = (x - mu_b) * (gamma * inv_b * r) + (beta + gamma * d)   [+ res] [relu]
 with mean / stdinv the running statistics of BEFORE the step's update. Batch norms run on unpadded channel counts only (a multiple
@@ -16,13 +16,14 @@ import subprocess
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as Fn
 
 from denet_amd import layer as layer_mod
 from denet_amd import ops
 from denet_amd.layer import Act, InitialLayer
 from denet_amd.layer.batch_norm import BatchNormLayer, renorm_limits
 from denet_amd.model import audit, model_cnn
+from fp64_model import build_model, param_layers as _param_layers, png_dataset as _png_dataset, reference as _reference
+from fp64_model import rel as _rel, sgd_step_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +35,10 @@ EPS = 1e-5
 @pytest.fixture(autouse=True)
 def _algorithm_tables_restored():
     """(as tests/test_activations_gpu.py) the per-geometry implementation tables are left as a fresh process has them"""
-    ops._load_tuned_once()
-    saved = (ops.POLICY, dict(ops._WINO), set(ops._TUNED))
     epoch = layer_mod.get_epoch()
-    yield
+    with ops.algorithms():
+        yield
     layer_mod.set_epoch(epoch)
-    ops.POLICY = saved[0]
-    ops._WINO.clear()
-    ops._WINO.update(saved[1])
-    ops._TUNED.clear()
-    ops._TUNED.update(saved[2])
 
 
 def _close(a, b, rtol=1e-3, atol=None):
@@ -56,11 +51,6 @@ def _close(a, b, rtol=1e-3, atol=None):
     tol = atol + rtol * b.abs()
     bad = err > tol
     assert not bad.any(), "max err %.3e (tol %.3e), %d/%d bad" % (float(err.max()), float(tol.min()), int(bad.sum()), bad.numel())
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max())
 
 
 def _batch_stats(x, eps):
@@ -273,19 +263,9 @@ ON_PARAM = {"renormMaxR": 3.0, "renormMaxD": 5.0, "renormMaxIt": 0}
 B, CLS, LR, MOM, DECAY = 4, 10, 0.1, 0.9, 0.0005
 
 
-def _build(bn_args, bn_param, seed=5):
-    np.random.seed(seed)
-    m = model_cnn.ModelCNN()
-    m.batch_size = B
-    m.class_num = CLS
-    m.build(STACK % (bn_args, bn_args), (3, 32, 32), "relu", "half", ["he-backward"])
-    rng = np.random.RandomState(seed + 1)
-    for l in model_cnn.walk_layers(m.layers):
-        if l.type_name == "batchnorm" and l.enabled:          # away from (gamma, beta) = (1, 0): both gradients carry weight
-            l.omega.set_value(rng.uniform(0.7, 1.3, l.omega.value.shape))
-            l.beta.set_value(rng.normal(0.0, 0.3, l.beta.value.shape))
-    head = m.layers[-2]
-    head.omega.set_value(head.omega.get_value() * 0.05)       # logits of order one (see tests/test_activations_gpu.py)
+def _build(bn_args, bn_param):
+    """batch norms away from (gamma, beta) = (1, 0), logits of order one (see tests/test_activations_gpu.py)"""
+    m = build_model(STACK % (bn_args, bn_args), (3, 32, 32), B, CLS, spread_bn=True, head_scale=0.05)
     j = m.export_json()
     for l in j["layers"]:
         if l["type"] == "resnet" and bn_param:
@@ -297,98 +277,6 @@ def _build(bn_args, bn_param, seed=5):
 
 def _bns(model):
     return [l for l in model_cnn.walk_layers(model.layers) if l.type_name == "batchnorm" and l.enabled]
-
-
-def _param_layers(model):
-    out = []
-    for l in model_cnn.walk_layers(model.layers):
-        if l.type_name == "conv":
-            out.append((l, [l.omega] + ([l.beta] if l.use_bias else [])))
-        elif l.type_name == "batchnorm" and l.enabled:
-            out.append((l, [l.omega, l.beta]))
-    return out
-
-
-def _reference(model, x, params, cls, train, running, draw=None):
-    """the stack in float64 on the host, wired like the layers themselves. running: {id(bn): (mean, stdinv)} BEFORE the step; a
-    batch norm missing from it gets statistics from draw(mu_b, inv_b). Returns (cost, logits, {id(bn): dict of its step})"""
-    val = {id(model.layers[0].output): torch.from_numpy(x).double()}
-    steps = {}
-
-    def run(l):
-        t = l.type_name
-        if t == "initial":
-            return
-        h = val[id(l.input)]
-        if t == "conv":
-            ps = params[id(l)]
-            h = Fn.conv2d(h, ps[0].flip(2, 3), stride=l.stride[0], padding=l.pad)      # (true convolution: convolution.py:80-83)
-            if l.use_bias:
-                h = h + ps[1][None, :, None, None]
-        elif t == "batchnorm":
-            gamma, beta = params[id(l)]
-            if train:
-                mu = h.mean(dim=(0, 2, 3))
-                inv = 1.0 / torch.sqrt(h.var(dim=(0, 2, 3), unbiased=False) + l.eps)
-                if id(l) not in running:
-                    running[id(l)] = draw(mu.detach(), inv.detach())
-                mean, stdinv = running[id(l)]
-                r = torch.ones_like(mu)
-                d = torch.zeros_like(mu)
-                if l.renorm_max_r > 1 or l.renorm_max_d > 0:
-                    r_max, d_max = l.renorm_max_r, l.renorm_max_d               # it = 0: open limits
-                    r = torch.clamp((1.0 / inv) * stdinv, 1.0 / r_max, r_max).detach()
-                    d = torch.clamp((mu - mean) * stdinv, -d_max, d_max).detach()
-                steps[id(l)] = {"r": r, "d": d, "rv": ((1.0 / inv) * stdinv).detach(), "dv": ((mu - mean) * stdinv).detach(),
-                                "run_mean": l.momentum * mean + (1 - l.momentum) * mu.detach(),
-                                "run_stdinv": l.momentum * stdinv + (1 - l.momentum) * inv.detach()}
-                h = (h - mu[None, :, None, None]) * (gamma * inv * r)[None, :, None, None] + (beta + gamma * d)[None, :, None, None]
-            else:
-                rm, rs = running[id(l)]
-                i2 = 1.0 / torch.sqrt((1.0 / rs) ** 2 + l.eps)                          # batch_norm.py:50-52: eps twice
-                h = (h - rm[None, :, None, None]) * (gamma * i2)[None, :, None, None] + beta[None, :, None, None]
-        elif t == "activation":
-            assert l.activation == "relu"
-            h = torch.relu(h)
-        elif t == "pool":
-            assert l.mode == "max"
-            h = Fn.max_pool2d(h, l.size[0], l.stride[0], l.pad[0])
-        elif t == "resnet":
-            assert "original" in l.version
-            for s in l.layers:
-                run(s)
-            y = val[id(l.layers[l.n_main - 1].output)]
-            sc = l.layers[l.n_main:]
-            xs = val[id(sc[-1].output)] if sc else h
-            h = torch.relu(xs + y)                                                      # resnet.py:109-113
-        elif t == "regression":
-            yc, xc = l.valid[0][1], l.valid[0][2]
-            logits = h[:, :, yc, xc]
-            lp = torch.log_softmax(logits, dim=1)
-            val["cost"] = -lp[torch.arange(len(cls)), torch.from_numpy(cls)].mean()
-            val["logits"] = logits
-            return
-        else:
-            raise AssertionError("unexpected layer " + t)
-        val[id(l.output)] = h
-
-    for l in model.layers:
-        run(l)
-    return val["cost"], val["logits"], steps
-
-
-class _direct_policy:
-    """every convolution pass on the direct kernels (exact fp32 FMA chains)"""
-
-    def __enter__(self):
-        self.saved = (ops.POLICY, dict(ops._WINO))
-        ops._WINO.clear()
-        ops.POLICY = lambda mode, g: 0
-
-    def __exit__(self, *a):
-        ops.POLICY = self.saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(self.saved[1])
 
 
 def _batch(seed=11):
@@ -403,7 +291,7 @@ def test_training_step_vs_fp64(hip, monkeypatch):
     block whose bnParam carries the keys (projection shortcut: res + ReLU + want_dres on its last batch norm), running statistics
     drawn so that every layer has clipped and unclipped channels: cost, gradients, updates, running statistics and the test-mode
     output afterwards within the project's 1e-3 max-norm budget of a float64 autograd restatement"""
-    with _direct_policy():
+    with ops.algorithms(table={}, POLICY=ops.direct_policy):
         model = _build(ON, ON_PARAM)
         bns = _bns(model)
         assert len(bns) == 5 and all(l.renorm_active for l in bns)
@@ -421,12 +309,12 @@ def test_training_step_vs_fp64(hip, monkeypatch):
         running = {}
         p0 = {k: [torch.from_numpy(v).double() for v in vs] for k, vs in values.items()}
         with torch.no_grad():
-            _reference(model, x, p0, cls, True, running, draw=lambda mu, inv: _draw_running(mu, inv, g, R, D, margin=1e-2)[:2])
+            _reference(model, x, p0, cls, True, running=running, draw=lambda mu, inv: _draw_running(mu, inv, g, R, D, margin=1e-2)[:2])
         for l in bns:
             l.mean.set_value(running[id(l)][0].numpy())
             l.stdinv.set_value(running[id(l)][1].numpy())
         params = {k: [torch.from_numpy(v).double().requires_grad_(True) for v in vs] for k, vs in values.items()}
-        cost_ref, _, steps = _reference(model, x, params, cls, True, running)
+        cost_ref, _, steps = _reference(model, x, params, cls, True, running=running)
         cost_ref.backward()
         for l in bns:
             _assert_clip_coverage(steps[id(l)]["rv"], steps[id(l)]["dv"], R, D)
@@ -441,17 +329,11 @@ def test_training_step_vs_fp64(hip, monkeypatch):
 
         e_cost = abs(cost - float(cost_ref.detach())) / abs(float(cost_ref.detach()))
         report, bad = [], []
-        for n, (l, ps) in enumerate(before):
-            for p, v, t in zip(ps, values[id(l)], params[id(l)]):
-                g_dev, g_ref = torch.from_numpy(p.get_grad().copy()).double(), t.grad
-                assert float(g_ref.abs().max()) > 0, (n, p.name)
-                v64 = torch.from_numpy(v).double()
-                p_ref = v64 - LR * (g_ref + (DECAY if id(p) in weights else 0.0) * v64)
-                p_dev = torch.from_numpy(p.get_value().copy()).double()
-                e_g, e_p = _rel(g_dev, g_ref), _rel(p_dev - v64, p_ref - v64)
-                report.append((e_g, e_p))
-                if not (e_g <= 1e-3 and e_p <= 1e-3):
-                    bad.append("#%d %s %s: grad %.2e, update %.2e" % (n, l.type_name, p.name, e_g, e_p))
+        for l, p, e_g, e_p, _, g_ref in sgd_step_errors(before, values, params, weights, LR, DECAY):
+            assert float(g_ref.abs().max()) > 0, (l.layer_index, p.name)
+            report.append((e_g, e_p))
+            if not (e_g <= 1e-3 and e_p <= 1e-3):
+                bad.append("L%d %s %s: grad %.2e, update %.2e" % (l.layer_index, l.type_name, p.name, e_g, e_p))
         print("cost %.6f (float64 %.6f, %.2e), worst gradient %.2e, worst update %.2e over %d arrays" % (
             cost, float(cost_ref.detach()), e_cost, max(r[0] for r in report), max(r[1] for r in report), len(report)))
         assert e_cost <= 1e-3, (cost, float(cost_ref.detach()))
@@ -469,7 +351,7 @@ def test_training_step_vs_fp64(hip, monkeypatch):
         # far from the batch's, so the soft-max may saturate: the logit map is the comparison that bites)
         now = {id(l): [torch.from_numpy(p.get_value().copy()).double() for p in ps] for l, ps in before}
         with torch.no_grad():
-            _, logits, _ = _reference(model, x, now, cls, False, after)
+            _, logits, _ = _reference(model, x, now, cls, False, running=after)
         pr_ref = torch.softmax(logits, dim=1)
         head = model.layers[-1].input
         for fold in (True, False):
@@ -533,18 +415,6 @@ def test_active_stack_runs_the_new_kernels_and_no_fusion(hip, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------- command line
-def _png_dataset(root, classes=3, per_class=4, seed=0):
-    from PIL import Image
-    rng = np.random.RandomState(seed)
-    for c in range(classes):
-        d = os.path.join(root, "class%i" % c)
-        os.makedirs(d)
-        for j in range(per_class):
-            img = rng.randint(0, 256, (32, 32, 3)).astype(np.uint8)
-            img[..., c] = 200 + 10 * (j % 5)
-            Image.fromarray(img).save(os.path.join(d, "img%i.png" % j))
-
-
 def test_cli_modify_train_predict(hip, tmp_path):
     """model-modify --modify-bn-renorm 3 5 10 on a small saved model, model-train for two epochs of three batches on it (the log
     line, the ramp at epoch 1, finite costs, the keys in the saved model), model-predict on the result and on the same weights

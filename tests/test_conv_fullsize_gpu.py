@@ -117,51 +117,44 @@ def test_conv_passes_at_benchmark_geometry(hip, geom):
     need_dx = C >= 32
     y_ref, dx_ref, dw_ref = _ref_fp64(x, w, dy, stride, pad, s_real, need_dx)
 
-    saved = (ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED))
     res = {}
-    try:
+    with ops.algorithms() as wino:
         g0 = ops.conv_geom(x.shape, w.shape, stride, pad, s_real)
         labels = [("direct", False), ("tuned", True)]
         if C == 64 and ops.conv_wino4t_ok(0, g0) and ops.conv_wino4t_ok(1, g0):
             labels.append(("fused4", True))        # what the committed file runs on the 64-channel stage: csrc/wino4t.hip (algorithm 44)
         for label, tuned in labels:
-            ops.AUTOTUNE = tuned
-            ops._WINO.clear()
+            wino.clear()
             ops._TUNED.clear()
             if label == "fused4":
-                ops._WINO[(0, g0)] = ops._WINO[(1, g0)] = ops.FUSED4
-            # "tuned": the algorithm of ops.static_policy (fused 64-channel / F(4x4) / F(2x2) wherever the geometry allows one - the
-            # widest kernel coverage; nothing is timed) on the launch configurations of the committed file
-            for rep in range(2):                                   # first call: decides and sets buffers up; second: the fixed choice alone
-                y = ops.conv_fwd(x, w, stride=stride, pad=pad, s_real=s_real)
-                dw = ops.conv_wgrad(x, dy, tuple(w.shape), stride=stride, pad=pad, s_real=s_real)
-                dx = ops.conv_dgrad(dy, w, tuple(x.shape), stride=stride, pad=pad, s_real=s_real) if need_dx else None
-            g = ops.conv_geom(x.shape, w.shape, stride, pad, s_real)
-            algo = {m: ops._WINO.get((i, g), 0) for i, m in enumerate(("fwd", "dgrad", "wgrad"))}
-            ent = {"fwd": _metrics(y, y_ref), "wgrad": _metrics(dw[:, :, :s_real, :], dw_ref), "algo": algo}
-            if need_dx:
-                ent["dgrad"] = _metrics(dx, dx_ref)
-            if S != s_real:
-                assert float(dw[:, :, s_real:, :].abs().max()) == 0.0
-            # the same forward pass with the batch-norm column sums written by its epilogue (what ConvLayer.forward runs in
-            # training): identical output, sums against fp64
-            cache = {"train": True}
-            y2 = ops.conv_fwd(x, w, stride=stride, pad=pad, s_real=s_real, cache=cache, bn_stats=True)
-            st = cache.get("bn_stats")
-            assert torch.equal(y2, y)
-            if st is not None:
-                part = st[0][:st[1] * 2 * K].view(st[1], 2, K).sum(0)
-                yd = y_ref.reshape(-1, K)
-                ent["bn_sums"] = (float((part[0] - yd.sum(0)).abs().max() / (yd.abs().sum(0).max() + 1e-30)),
-                                  float((part[1] - (yd * yd).sum(0)).abs().max() / (yd * yd).sum(0).max()))
-                assert ent["bn_sums"][0] <= 1e-5 and ent["bn_sums"][1] <= 1e-5, (name, label, ent["bn_sums"])
-            res[label] = ent
-    finally:
-        ops.AUTOTUNE = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
-        ops._TUNED.clear()
-        ops._TUNED.update(saved[2])
+                wino[(0, g0)] = wino[(1, g0)] = ops.FUSED4
+            with ops.switches(AUTOTUNE=tuned):
+                # "tuned": the algorithm of ops.static_policy (fused 64-channel / F(4x4) / F(2x2) wherever the geometry allows one - the
+                # widest kernel coverage; nothing is timed) on the launch configurations of the committed file
+                for rep in range(2):                                   # first call: decides and sets buffers up; second: the fixed choice alone
+                    y = ops.conv_fwd(x, w, stride=stride, pad=pad, s_real=s_real)
+                    dw = ops.conv_wgrad(x, dy, tuple(w.shape), stride=stride, pad=pad, s_real=s_real)
+                    dx = ops.conv_dgrad(dy, w, tuple(x.shape), stride=stride, pad=pad, s_real=s_real) if need_dx else None
+                g = ops.conv_geom(x.shape, w.shape, stride, pad, s_real)
+                algo = {m: ops._WINO.get((i, g), 0) for i, m in enumerate(("fwd", "dgrad", "wgrad"))}
+                ent = {"fwd": _metrics(y, y_ref), "wgrad": _metrics(dw[:, :, :s_real, :], dw_ref), "algo": algo}
+                if need_dx:
+                    ent["dgrad"] = _metrics(dx, dx_ref)
+                if S != s_real:
+                    assert float(dw[:, :, s_real:, :].abs().max()) == 0.0
+                # the same forward pass with the batch-norm column sums written by its epilogue (what ConvLayer.forward runs in
+                # training): identical output, sums against fp64
+                cache = {"train": True}
+                y2 = ops.conv_fwd(x, w, stride=stride, pad=pad, s_real=s_real, cache=cache, bn_stats=True)
+                st = cache.get("bn_stats")
+                assert torch.equal(y2, y)
+                if st is not None:
+                    part = st[0][:st[1] * 2 * K].view(st[1], 2, K).sum(0)
+                    yd = y_ref.reshape(-1, K)
+                    ent["bn_sums"] = (float((part[0] - yd.sum(0)).abs().max() / (yd.abs().sum(0).max() + 1e-30)),
+                                      float((part[1] - (yd * yd).sum(0)).abs().max() / (yd * yd).sum(0).max()))
+                    assert ent["bn_sums"][0] <= 1e-5 and ent["bn_sums"][1] <= 1e-5, (name, label, ent["bn_sums"])
+                res[label] = ent
     RESULTS[name] = res
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     with open(OUT, "w") as f:

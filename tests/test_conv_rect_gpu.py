@@ -19,6 +19,7 @@ from denet_amd import ops
 from denet_amd.lib import DenetHipError
 from denet_amd.model import model_cnn
 from denet_amd.model.audit import KernelAudit
+from fp64_model import build_model, param_layers, reference, rel as _rel, relu_masks_of, sgd_step_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +27,6 @@ FILTERS = [(1, 7), (7, 1), (1, 3), (3, 1), (3, 5), (2, 3), (3, 3)]
 STRIDES = [(1, 1), (2, 1), (1, 2), (2, 2), (4, 1)]
 BORDERS = ["valid", "half", "full", "same"]
 BOUND = 1e-5
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max())
 
 
 def _padding(border, R, S):
@@ -182,18 +178,10 @@ def test_rect_agrees_with_square_direct_kernels(hip, k, stride, pad, ohw):
     geom = ops.conv_geom(tuple(x.shape), tuple(w.shape), stride, pad, None, ohw)
     dy = torch.randn(N, geom[10], geom[11], K, generator=g).cuda()
     bias = torch.randn(K, generator=g).cuda()
-    ops._load_tuned_once()             # (before the table is emptied: the first decision would load the committed file)
-    saved = (ops.POLICY, dict(ops._WINO))
-    ops._WINO.clear()
-    ops.POLICY = lambda mode, gg: 0
-    try:
+    with ops.algorithms(table={}, POLICY=ops.direct_policy):
         y0 = ops.conv_fwd(x, w, bias=bias, stride=stride, pad=pad, ohw=ohw)
         dx0 = ops.conv_dgrad(dy, w, tuple(x.shape), stride=stride, pad=pad, ohw=ohw)
         dw0 = ops.conv_wgrad(x, dy, tuple(w.shape), stride=stride, pad=pad, ohw=ohw)
-    finally:
-        ops.POLICY = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
     kw = dict(stride=(stride, stride), pad=(pad, pad), ohw=ohw)
     y1 = ops.conv_rect_fwd(x, w, bias=bias, **kw)
     dx1 = ops.conv_rect_dgrad(dy, w, tuple(x.shape), **kw)
@@ -240,63 +228,9 @@ MIXED_MAPS = [(16, 24), (16, 24), (8, 24), (16, 24), (16, 12), (1, 1)]      # C.
 
 
 def _mixed_model(B, CLS, seed):
-    np.random.seed(seed)
-    m = model_cnn.ModelCNN()
-    m.batch_size, m.class_num = B, CLS
-    m.build(MIXED_DESC, (3, 16, 24), "relu", "half", ["he-backward"])
+    m = build_model(MIXED_DESC, (3, 16, 24), B, CLS, seed=seed)
     m.class_labels = {"c%i" % i: i for i in range(CLS)}
     return m
-
-
-def _mixed_reference(model, x, params, cls, train=True, running=None, relu_masks=None, flips=None, outs=None):
-    """the mixed model in float64 on the host (params[i]: the reference-layout arrays of layer i). relu_masks / flips as
-    tests/test_simple_cifar10_gpu.py: the device's ReLU decisions, teacher-forced, and the count of those float64 disagrees with.
-    outs[i] (training): the output of convolution i, its gradient retained"""
-    h = torch.from_numpy(x).double()
-    stats = {}
-    for i, l in enumerate(model.layers[1:], start=1):
-        t = l.type_name
-        if t == "conv":
-            R, S = l.filter_shape[2:]
-            pad = _padding(l.border_mode, R, S)
-            h = Fn.conv2d(h, params[i][0].flip(2, 3), stride=l.stride, padding=pad)
-            if l.use_bias:
-                h = h + params[i][1][None, :, None, None]
-            if outs is not None:
-                h.retain_grad()
-                outs[i] = h
-        elif t == "deconv":
-            R, S = l.filter_shape[2:]
-            wt = torch.flip(params[i][0].permute(1, 0, 2, 3), [2, 3])
-            h = Fn.conv_transpose2d(h, wt, params[i][1], stride=l.stride, padding=(R // 2, S // 2),
-                                    output_padding=(l.stride[0] - 1, l.stride[1] - 1))
-        elif t == "batchnorm":
-            gamma, beta = params[i]
-            if train:
-                mean = h.mean(dim=(0, 2, 3))
-                var = h.var(dim=(0, 2, 3), unbiased=False)
-                stats[i] = (mean.detach(), 1.0 / torch.sqrt(var.detach() + l.eps))
-                h = (h - mean[None, :, None, None]) / torch.sqrt(var + l.eps)[None, :, None, None]
-            else:
-                rm, rs = running[i]
-                inv = 1.0 / torch.sqrt((1.0 / rs) ** 2 + l.eps)          # batch_norm.py:50-52: eps twice
-                h = (h - rm[None, :, None, None]) * inv[None, :, None, None]
-            h = h * gamma[None, :, None, None] + beta[None, :, None, None]
-        elif t == "activation":
-            if relu_masks is None:
-                h = torch.relu(h)
-            else:
-                m = relu_masks[i].double()
-                if flips is not None:
-                    flips[i] = int(((h.detach() > 0).double() != m).sum())
-                h = h * m
-        elif t == "regression":
-            logits = h[:, :, 0, 0]
-            lp = torch.log_softmax(logits, dim=1)
-            return -lp[torch.arange(len(cls)), torch.from_numpy(cls)].mean(), logits, stats
-        else:
-            raise AssertionError("unexpected layer " + t)
-        assert tuple(h.shape) == tuple(l.output_shape), (i, t, h.shape, l.output_shape)
 
 
 def test_mixed_model_training_step_and_inference_vs_fp64(hip, tmp_path):
@@ -315,13 +249,8 @@ def test_mixed_model_training_step_and_inference_vs_fp64(hip, tmp_path):
     cls = rng.randint(0, CLS, B)
     metas = [{"image_class": int(c)} for c in cls]
     weights = set(id(p) for l in model.layers for p in l.weights())
-    before = {}
-    for i, l in enumerate(model.layers):
-        if l.type_name in ("conv", "deconv"):
-            before[i] = [l.omega] + ([l.beta] if l.use_bias else [])
-        elif l.type_name == "batchnorm":
-            before[i] = [l.omega, l.beta]
-    values = {i: [p.get_value().copy() for p in ps] for i, ps in before.items()}
+    before = param_layers(model)
+    values = {id(l): [p.get_value().copy() for p in ps] for l, ps in before}
 
     with KernelAudit(model) as audit:
         cost, _ = model.train_step(x, metas, 0, 0, LR, [MOM], DECAY)
@@ -340,52 +269,43 @@ def test_mixed_model_training_step_and_inference_vs_fp64(hip, tmp_path):
     assert sorted(s[:19] for s in audit.other if s.startswith("conv_rect")) == ["conv_rect_kernel<0,", "conv_rect_kernel<1,",
                                                                                   "conv_rect_kernel<2,"], audit.other
 
-    relu_masks = {}
-    for i, l in enumerate(model.layers):
-        if l.type_name == "activation":
-            d = l.output._data
-            assert d is not None, i
-            relu_masks[i] = (d[..., :l.output_shape[1]] > 0).permute(0, 3, 1, 2).cpu()
-    params = {i: [torch.from_numpy(v).double().requires_grad_(True) for v in vs] for i, vs in values.items()}
+    relu_masks = relu_masks_of(model)
+    params = {k: [torch.from_numpy(v).double().requires_grad_(True) for v in vs] for k, vs in values.items()}
     flips, outs = {}, {}
-    cost_ref, _, stats = _mixed_reference(model, x, params, cls, relu_masks=relu_masks, flips=flips, outs=outs)
+    cost_ref, _, stats = reference(model, x, params, cls, True, relu_masks=relu_masks, flips=flips, outs=outs)
     cost_ref.backward()
-    print("ReLU decisions that differ from float64 (layer: count):", {i: n for i, n in flips.items() if n})
+    print("ReLU decisions that differ from float64 (layer: count):", {l.layer_index: flips[id(l)] for l in model.layers if flips.get(id(l))})
     print("cost", cost, float(cost_ref.detach()))
     assert abs(cost - float(cost_ref.detach())) <= 1e-3 * abs(float(cost_ref.detach())), (cost, float(cost_ref.detach()))
     report, bad = [], []
-    for i, ps in before.items():
-        for p, v, t in zip(ps, values[i], params[i]):
-            g_dev = torch.from_numpy(p.get_grad().copy()).double()
-            g_ref = t.grad
-            dec = DECAY if id(p) in weights else 0.0
-            v64 = torch.from_numpy(v).double()
-            p_ref = v64 - LR * (g_ref + dec * v64)
+    for l, p, e_g, e_p, g_dev, g_ref in sgd_step_errors(before, values, params, weights, LR, DECAY):
+        i = l.layer_index
+        if p is getattr(l, "beta", None) and l.type_name == "conv" and model.layers[i + 1].type_name == "batchnorm":
+            # a bias in front of a batch norm: the normalisation removes it, its exact gradient is 0 (float64 leaves 1e-17)
+            # and max|b| is no scale. The gradient is the column sum of dy: the error is taken against the largest
+            # sum of |dy| over a channel, the magnitude those sums are formed from (an fp32 sum errs by eps times that)
+            scale = float(outs[id(l)].grad.abs().sum(dim=(0, 2, 3)).max())
+            v64 = torch.from_numpy(values[id(l)][1]).double()
             p_dev = torch.from_numpy(p.get_value().copy()).double()
-            e_g, e_p = _rel(g_dev, g_ref), _rel(p_dev - v64, p_ref - v64)
-            if p is getattr(model.layers[i], "beta", None) and model.layers[i].type_name == "conv" \
-                    and model.layers[i + 1].type_name == "batchnorm":
-                # a bias in front of a batch norm: the normalisation removes it, its exact gradient is 0 (float64 leaves 1e-17)
-                # and max|b| is no scale. The gradient is the column sum of dy: the error is taken against the largest
-                # sum of |dy| over a channel, the magnitude those sums are formed from (an fp32 sum errs by eps times that)
-                scale = float(outs[i].grad.abs().sum(dim=(0, 2, 3)).max())
-                e_g = float((g_dev - g_ref).abs().max()) / scale
-                e_p = float(((p_dev - v64) - (p_ref - v64)).abs().max()) / (LR * scale)
-                print("L%d bias in front of a batch norm: |grad| device %.2e float64 %.2e, sum|dy| %.2e" % (
-                    i, float(g_dev.abs().max()), float(g_ref.abs().max()), scale))
-            report.append("L%d %s %s: grad %.2e, update %.2e" % (i, model.layers[i].type_name, p.name, e_g, e_p))
-            if not (e_g <= 1e-3 and e_p <= 1e-3):
-                bad.append(report[-1])
+            p_ref = v64 - LR * (g_ref + (DECAY if id(p) in weights else 0.0) * v64)
+            e_g = float((g_dev - g_ref).abs().max()) / scale
+            e_p = float(((p_dev - v64) - (p_ref - v64)).abs().max()) / (LR * scale)
+            print("L%d bias in front of a batch norm: |grad| device %.2e float64 %.2e, sum|dy| %.2e" % (
+                i, float(g_dev.abs().max()), float(g_ref.abs().max()), scale))
+        report.append("L%d %s %s: grad %.2e, update %.2e" % (i, l.type_name, p.name, e_g, e_p))
+        if not (e_g <= 1e-3 and e_p <= 1e-3):
+            bad.append(report[-1])
     print("\n".join(report))
     assert not bad, bad
 
     running = {}
-    for i, l in enumerate(model.layers):
+    for l in model.layers:
         if l.type_name == "batchnorm":
             rm, rs = torch.from_numpy(l.mean.get_value().copy()).double(), torch.from_numpy(l.stdinv.get_value().copy()).double()
-            m_ref, s_ref = (1.0 - l.momentum) * stats[i][0], l.momentum + (1.0 - l.momentum) * stats[i][1]
-            assert _rel(rm, m_ref) <= 1e-3 and _rel(rs, s_ref) <= 1e-3, i
-            running[i] = (rm, rs)
+            m_ref = (1.0 - l.momentum) * stats[id(l)]["mean"]
+            s_ref = l.momentum + (1.0 - l.momentum) * stats[id(l)]["stdinv"]
+            assert _rel(rm, m_ref) <= 1e-3 and _rel(rs, s_ref) <= 1e-3, l.layer_index
+            running[id(l)] = (rm, rs)
 
     # inference: the batch norms behind the rectangular layers are folded into conv_rect_fwd's epilogue
     assert ops.INFER_FOLD
@@ -394,9 +314,9 @@ def test_mixed_model_training_step_and_inference_vs_fp64(hip, tmp_path):
         torch.cuda.synchronize()
     for r in audit.table[1:]:
         assert len(r["fwd"]) == 1 and r["fwd"][0].startswith("conv_rect_kernel<0, "), r
-    now = {i: [torch.from_numpy(p.get_value().copy()).double() for p in ps] for i, ps in before.items()}
+    now = {id(l): [torch.from_numpy(p.get_value().copy()).double() for p in ps] for l, ps in before}
     with torch.no_grad():
-        _, logits, _ = _mixed_reference(model, x, now, cls, train=False, running=running)
+        _, logits, _ = reference(model, x, now, cls, False, running=running)
     pr_ref = torch.softmax(logits, dim=1)
     assert pr.shape == (B, CLS)
     e_pr = float((torch.from_numpy(pr).double() - pr_ref).abs().max()) / float(pr_ref.max())
@@ -417,11 +337,8 @@ def test_mixed_model_training_step_and_inference_vs_fp64(hip, tmp_path):
 
 def test_classifier_head_behind_non_square_map_trains(hip):
     """`C[32,3] R` on a 3 x 16 x 20 input: the head's whole-map `valid` convolution (16 x 20) runs the rectangular kernels"""
-    np.random.seed(1)
     B, CLS = 4, 6
-    m = model_cnn.ModelCNN()
-    m.batch_size, m.class_num = B, CLS
-    m.build("C[32,3] R", (3, 16, 20), "relu", "half", ["he-backward"])
+    m = build_model("C[32,3] R", (3, 16, 20), B, CLS, seed=1)
     head = m.layers[2]
     assert head.filter_shape == (CLS, 32, 16, 20) and head.anisotropic and head.output_shape == (B, CLS, 1, 1)
     m.build_train_func("sgd")
@@ -430,9 +347,7 @@ def test_classifier_head_behind_non_square_map_trains(hip):
     cls = rng.randint(0, CLS, B)
     w0, w1 = [torch.from_numpy(l.omega.get_value().copy()).double().requires_grad_(True) for l in m.layers[1:3]]
     cost, _ = m.train_step(x, [{"image_class": int(c)} for c in cls], 0, 0, 0.1, [0.9], 0.0)
-    h = Fn.conv2d(torch.from_numpy(x).double(), w0.flip(2, 3), padding=1)
-    logits = Fn.conv2d(h, w1.flip(2, 3))[:, :, 0, 0]
-    cost_ref = -torch.log_softmax(logits, dim=1)[torch.arange(B), torch.from_numpy(cls)].mean()
+    cost_ref, _, _ = reference(m, x, {id(m.layers[1]): [w0], id(m.layers[2]): [w1]}, cls, True)
     cost_ref.backward()
     assert abs(cost - float(cost_ref.detach())) <= 1e-3 * abs(float(cost_ref.detach()))
     for l, t in zip(m.layers[1:3], (w0, w1)):

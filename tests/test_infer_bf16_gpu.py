@@ -9,6 +9,7 @@ import torch
 from bf16_reference import check_fwd, draw, ties
 from denet_amd import ops
 from denet_amd.model import audit, model_cnn, update_bn, zoo
+from fp64_model import build_model
 
 pytestmark = pytest.mark.gpu
 
@@ -98,10 +99,7 @@ STACK_B, STACK_IMG, STACK_CLASSES = 4, 16, 10
 
 
 def _build(desc, seed=5):
-    np.random.seed(seed)
-    m = model_cnn.ModelCNN()
-    m.batch_size, m.class_num = STACK_B, STACK_CLASSES
-    m.build(desc, (3, STACK_IMG, STACK_IMG), "relu", "half", ["he-backward"])
+    m = build_model(desc, (3, STACK_IMG, STACK_IMG), STACK_B, STACK_CLASSES, seed=seed, head_scale=0.05)
     rng = np.random.RandomState(seed + 1)
     for l in model_cnn.walk_layers(m.layers):
         if l.type_name in ("batchnorm", "batchnorm-relu") and l.enabled:
@@ -110,8 +108,6 @@ def _build(desc, seed=5):
             l.stdinv.set_value(rng.uniform(0.7, 1.4, C).astype(np.float32))
             l.omega.set_value(rng.uniform(0.7, 1.3, C).astype(np.float32))
             l.beta.set_value(rng.normal(0.0, 0.3, C).astype(np.float32))
-    head = m.layers[-2]
-    head.omega.set_value(head.omega.get_value() * 0.05)      # logits of order one: the softmax does not saturate
     return m
 
 

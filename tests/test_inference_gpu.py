@@ -274,10 +274,8 @@ def test_inference_bn_folding_matches_unfolded(hip):
             l.beta.set_value(rng.normal(0, 0.2, C).astype(np.float32))
     x, _ = zoo.synthetic_batch(B, IMG, seed=2)
     outs = []
-    saved = ops.INFER_FOLD
-    try:
-        for fold in (False, True):
-            ops.INFER_FOLD = fold
+    for fold in (False, True):
+        with ops.infer_fold(fold):
             for l in model_cnn_walk(model):
                 l.__dict__.pop("_plan", None)
             model.forward(x, None, train=False)
@@ -285,8 +283,6 @@ def test_inference_bn_folding_matches_unfolded(hip):
             res = [l for l in model.layers if l.type_name == "resnet"]
             outs.append([ops.nhwc_to_nchw(a.output.data, a.output_shape[1]).cpu().numpy() for a in (res[0], res[7], res[-1])] +
                         [dnc.corner_pr.cpu().numpy(), ops.nhwc_to_nchw(model.layers[2].output.data, 64).cpu().numpy()])
-    finally:
-        ops.INFER_FOLD = saved
     for a, b in zip(*outs):
         scale = float(np.abs(a).max())
         assert float(np.abs(a - b).max()) <= 2e-5 * scale + 1e-6, (float(np.abs(a - b).max()), scale)
@@ -314,28 +310,22 @@ def test_inference_forward_at_the_batch_of_the_tuned_file(hip):
     dnd.layers[0].omega.set_value(rng.normal(0, 0.02, dnd.layers[0].omega.value.shape))
     x, metas = zoo.synthetic_batch(B, 512, 80, seed=1)
     xd = torch.from_numpy(x).cuda()
-    ops._load_tuned_once()
-    saved = (ops.WINO4T, dict(ops._WINO))
     outs, kernels = [], []
-    try:
+    with ops.algorithms() as wino:
         for on in (True, False):
             if not on:
-                ops.WINO4T = 0
-                for k in [k for k, v in ops._WINO.items() if v == ops.FUSED4]:
-                    del ops._WINO[k]                       # (what load_tuned does with entries the switches exclude: decided afresh)
-            for l in model_cnn_walk(model):
-                l.__dict__.pop("_plan", None)
-            with audit.KernelAudit(model) as ka:
-                model.forward(xd, None, train=False)
-                torch.cuda.synchronize()
-            kernels.append({g: tuple(e["fwd"]) for g, e in ka.summary().items()})
-            dns = [l for l in model.layers if l.type_name == "denet-sparse"][0]
-            outs.append((dnc.corner_pr.cpu().numpy().copy(), dnc.conv.output.data.float().cpu().numpy().copy(),
-                         dnd.conv.output.data.float().cpu().numpy().copy(), [list(l) for l in dns.sample_bbox_list]))
-    finally:
-        ops.WINO4T = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
+                for k in [k for k, v in wino.items() if v == ops.FUSED4]:
+                    del wino[k]                            # (what load_tuned does with entries the switches exclude: decided afresh)
+            with ops.switches(WINO4T=ops.WINO4T if on else 0):
+                for l in model_cnn_walk(model):
+                    l.__dict__.pop("_plan", None)
+                with audit.KernelAudit(model) as ka:
+                    model.forward(xd, None, train=False)
+                    torch.cuda.synchronize()
+                kernels.append({g: tuple(e["fwd"]) for g, e in ka.summary().items()})
+                dns = [l for l in model.layers if l.type_name == "denet-sparse"][0]
+                outs.append((dnc.corner_pr.cpu().numpy().copy(), dnc.conv.output.data.float().cpu().numpy().copy(),
+                             dnd.conv.output.data.float().cpu().numpy().copy(), [list(l) for l in dns.sample_bbox_list]))
     used = [g for g, k in kernels[0].items() if any(n.startswith("wino4t_kernel") for n in k)]
     assert len(used) >= 5, kernels[0]                      # the 64-channel stage + the four mode-3 geometries
     assert not any(n.startswith("wino4t_kernel") for k in kernels[1].values() for n in k)
@@ -402,8 +392,6 @@ def test_inference_after_training_steps_matches_a_fresh_model(hip, k):
     _warm_corner_head(model, 4.0, 0.3)
     x, metas = zoo.synthetic_batch(B, IMG, 20, seed=2)
     xd = torch.from_numpy(x).cuda()
-    ops._load_tuned_once()
-    saved = dict(ops._WINO)
     geoms = _mode3_geometries(model)
     assert len(geoms) >= 2, geoms
 
@@ -414,9 +402,9 @@ def test_inference_after_training_steps_matches_a_fresh_model(hip, k):
         s = [l for l in m.layers if l.type_name == "denet-sparse"][0]
         return c.corner_pr.clone(), d.conv.output.data.clone(), [list(l) for l in s.sample_bbox_list]
 
-    try:
+    with ops.algorithms() as wino:
         for g in geoms:
-            ops._WINO[(3, g)] = ops.FUSED4
+            wino[(3, g)] = ops.FUSED4
         model.build_train_func("nesterov")
         infer(model)
         assert sum(l._cache().get("fwd_tile") == ops.FUSED4 for _, l in audit.conv_layers(model)) >= len(geoms), \
@@ -427,9 +415,6 @@ def test_inference_after_training_steps_matches_a_fresh_model(hip, k):
         got = infer(model)
         fresh = model_cnn.load_from_json(model.export_json(), B)
         want = infer(fresh)
-    finally:
-        ops._WINO.clear()
-        ops._WINO.update(saved)
     assert got[2] == want[2], "RoI lists differ"
     assert any(len(l) for l in want[2])
     assert torch.equal(got[0], want[0]), "corner map: %.3e" % float((got[0] - want[0]).abs().max())
@@ -442,16 +427,15 @@ def test_wino4t_switch_routes_the_committed_inference_entries(hip, monkeypatch, 
     gradients only): the inference forward pass at a mode-3 geometry runs the tile-parallel kernel exactly when the forward bit is
     set; the data gradient of the 64-channel stage keeps it exactly when the data-gradient bit is set"""
     ops._load_tuned_once()
-    saved = dict(ops._WINO)
-    m3 = sorted(g for (m, g), t in saved.items() if m == 3 and t == ops.FUSED4)
-    d4 = sorted(g for (m, g), t in saved.items() if m == 1 and t == ops.FUSED4)
+    committed = dict(ops._WINO)
+    m3 = sorted(g for (m, g), t in committed.items() if m == 3 and t == ops.FUSED4)
+    d4 = sorted(g for (m, g), t in committed.items() if m == 1 and t == ops.FUSED4)
     assert m3 and d4
     g = min(m3, key=lambda g: g[0] * g[1] * g[2] * (g[3] + g[4]))
     gd = min(d4, key=lambda g: g[0] * g[1] * g[2] * (g[3] + g[4]))
     monkeypatch.setattr(ops, "WINO4T", wino4t)
     gen = torch.Generator().manual_seed(wino4t)
-    try:
-        ops._WINO.clear()
+    with ops.algorithms(table={}):
         ops.load_tuned(ops.TUNE_CACHE)
         assert ((3, g) in ops._WINO) == bool(wino4t & 1) and ((1, gd) in ops._WINO) == bool(wino4t & 2)
         N, H, W, C, K = g[:5]
@@ -460,7 +444,7 @@ def test_wino4t_switch_routes_the_committed_inference_entries(hip, monkeypatch, 
         icache = {}
         ops.conv_fwd(x, w, bias=torch.zeros(K, device="cuda"), stride=1, pad=1, relu=True, cache=icache)
         assert (icache["fwd_tile"] == ops.FUSED4) == bool(wino4t & 1), (wino4t, icache["fwd_tile"])
-        assert icache["fwd_tile"] == (ops.FUSED4 if wino4t & 1 else saved[(0, g)])
+        assert icache["fwd_tile"] == (ops.FUSED4 if wino4t & 1 else committed[(0, g)])
         del x
         N, H, W, C, K = gd[:5]
         dy = torch.randn(N, H, W, K, generator=gen).cuda()
@@ -468,9 +452,6 @@ def test_wino4t_switch_routes_the_committed_inference_entries(hip, monkeypatch, 
         dcache = {"train": True}
         ops.conv_dgrad(dy, w, (N, H, W, C), stride=1, pad=1, cache=dcache)
         assert (dcache["dgrad_tile"] == ops.FUSED4) == bool(wino4t & 2), (wino4t, dcache["dgrad_tile"])
-    finally:
-        ops._WINO.clear()
-        ops._WINO.update(saved)
 
 
 def _chunk_nchw(t, B, sl, shape):

@@ -87,13 +87,12 @@ def test_conv_epilogue_statistics_with_a_large_channel_offset(hip, ratio):
     gamma, beta = torch.ones(K).cuda(), torch.zeros(K).cuda()
     y0 = ops.conv_fwd(x, w, stride=1, pad=1)
     bias = (float(ratio) * y0.std()).item() * torch.ones(K).cuda()
-    saved = dict(ops._WINO)
-    try:
+    with ops.algorithms() as wino:
         worst = 0.0
         for force in (0, 2, 4, 22):
             geom = ops.conv_geom(x.shape, w.shape, 1, 1, None)
-            ops._WINO.clear()
-            ops._WINO[(0, geom)] = force
+            wino.clear()
+            wino[(0, geom)] = force
             cache = {"train": True}
             y = ops.conv_fwd(x, w, bias=bias, stride=1, pad=1, cache=cache, bn_stats=True)
             st = cache.get("bn_stats")
@@ -104,9 +103,6 @@ def test_conv_epilogue_statistics_with_a_large_channel_offset(hip, ratio):
             err = float(((si.double() - ref) / ref).abs().max())
             print("ratio %g, algorithm %d: %.2e" % (ratio, force, err))
             worst = max(worst, err)
-    finally:
-        ops._WINO.clear()
-        ops._WINO.update(saved)
     # the first layer (7x7 / 2 from the planar batch, the only biased convolution in front of a batch norm: C.B[64,7,2] BN)
     xs = torch.rand(2, 3, 128, 128, generator=g).cuda()
     ws = torch.zeros(64, 7, 8, 4)
@@ -142,14 +138,13 @@ def test_conv_epilogue_batch_norm_sums(hip, case):
     OH = (H + 2 * pad - R) // stride + 1
     addt = torch.randn(N, OH, OH if H == W else (W + 2 * pad - R) // stride + 1, K, generator=g).cuda()
     gamma, beta = torch.rand(K, generator=g).cuda() + 0.5, torch.randn(K, generator=g).cuda()
-    saved = (ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED))
-    try:
+    with ops.algorithms() as wino:
         for force_wino in (0, 2, 4):
             geom = ops.conv_geom(x.shape, w.shape, stride, pad, None)
             if force_wino and not ops.conv_wino_ok(geom, force_wino):
                 continue
-            ops._WINO.clear()
-            ops._WINO[(0, geom)] = force_wino
+            wino.clear()
+            wino[(0, geom)] = force_wino
             cache = {"train": True}
             y = ops.conv_fwd(x, w, bias=bias, add=addt, stride=stride, pad=pad, cache=cache, bn_stats=True)
             st = cache.get("bn_stats")
@@ -170,10 +165,6 @@ def test_conv_epilogue_batch_norm_sums(hip, case):
             torch.testing.assert_close(sm, sm2, rtol=1e-5, atol=1e-6)
             torch.testing.assert_close(si, si2, rtol=1e-5, atol=1e-6)
             torch.testing.assert_close(rs, rs2, rtol=1e-5, atol=1e-6)
-    finally:
-        ops.AUTOTUNE = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
 
 
 @pytest.mark.parametrize("case", [(1, 16, 16, 64), (2, 32, 48, 64), (1, 16, 32, 128), (5, 128, 128, 64), (3, 128, 64, 128), (14, 128, 128, 64),
@@ -193,11 +184,7 @@ def test_fused_winograd_f2_kernel(hip, case):
     addt = torch.randn(N, H, W, Co, generator=gen).cuda()
     g = ops.conv_geom(x.shape, w.shape, 1, 1, None)
     assert ops.conv_wino2f_ok(0, g) and ops.conv_wino2f_ok(1, g) == (Co == 64)
-    saved = (ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED))
-    try:
-        ops._WINO.clear()
-        ops._WINO[(0, g)] = ops.FUSED2
-        ops._WINO[(1, g)] = ops.FUSED2 if Co == 64 else 0
+    with ops.algorithms(table={(0, g): ops.FUSED2, (1, g): ops.FUSED2 if Co == 64 else 0}) as wino:
         xd, wd = x.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True), w.double().permute(0, 3, 1, 2)
         ref = Fn.conv2d(xd, wd, None, padding=1)
         r = ref.detach().permute(0, 2, 3, 1)
@@ -226,7 +213,7 @@ def test_fused_winograd_f2_kernel(hip, case):
             assert float((dx.double() - rdx).abs().max()) / float(rdx.abs().max()) <= 1e-6
             # the filter gradient, fused the same way (64 -> 64 only): sums over all N * H * W / 4 tiles
             assert ops.conv_wino2f_ok(2, g)
-            ops._WINO[(2, g)] = ops.FUSED2
+            wino[(2, g)] = ops.FUSED2
             wd2 = w.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True)
             rdw = torch.autograd.grad(Fn.conv2d(xd.detach(), wd2, None, padding=1), wd2, dy.double().permute(0, 3, 1, 2))[0]
             rdw = rdw.permute(0, 2, 3, 1)
@@ -236,10 +223,6 @@ def test_fused_winograd_f2_kernel(hip, case):
             assert torch.equal(dw, dw2)                                   # partial sums are added in a fixed order
         else:
             assert not ops.conv_wino2f_ok(2, g)
-    finally:
-        ops.AUTOTUNE = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
 
 
 @pytest.mark.parametrize("case", [(1, 8, 32, 64, 64), (2, 16, 64, 64, 64), (3, 12, 20, 64, 64), (2, 24, 40, 32, 128), (1, 16, 32, 128, 64),
@@ -266,11 +249,8 @@ def test_fused_winograd_f4_tile_parallel_kernel(hip, case):
     addt = torch.randn(N, H, W, K, generator=gen).cuda()
     g = ops.conv_geom(x.shape, w.shape, 1, 1, None)
     assert ops.conv_wino4t_ok(0, g) and ops.conv_wino4t_ok(1, g) == (C % 64 == 0 and K % 16 == 0)
-    saved = (ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED))
     BOUND = 8e-5
-    try:
-        ops._WINO.clear()
-        ops._WINO[(0, g)] = ops.FUSED4
+    with ops.algorithms(table={(0, g): ops.FUSED4}) as wino:
         xd, wd = x.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True), w.double().permute(0, 3, 1, 2)
         ref = Fn.conv2d(xd, wd, None, padding=1)
         r = ref.detach().permute(0, 2, 3, 1)
@@ -303,8 +283,8 @@ def test_fused_winograd_f4_tile_parallel_kernel(hip, case):
         assert float((y6.double() - r6).abs().max()) / float(r6.abs().max()) <= BOUND
         assert bool((y6 >= 0).all()) and bool((y6 == 0).any())
         # ... and a mode-3 entry of the tuned file overrides the training decision for the inference forward pass only
-        ops._WINO[(0, g)] = 0
-        ops._WINO[(3, g)] = ops.FUSED4
+        wino[(0, g)] = 0
+        wino[(3, g)] = ops.FUSED4
         icache = {}
         y5 = ops.conv_fwd(x, w, bias=bias, stride=1, pad=1, relu=True, cache=icache)
         assert torch.equal(y5, y3) and icache["fwd_tile"] == ops.FUSED4
@@ -314,10 +294,10 @@ def test_fused_winograd_f4_tile_parallel_kernel(hip, case):
         tcache = {"train": True}
         ops.conv_fwd(x, w, bias=bias, stride=1, pad=1, relu=True, cache=tcache)
         assert tcache["fwd_tile"] == 0
-        ops._WINO[(0, g)] = ops.FUSED4
-        del ops._WINO[(3, g)]
+        wino[(0, g)] = ops.FUSED4
+        del wino[(3, g)]
         if ops.conv_wino4t_ok(1, g):
-            ops._WINO[(1, g)] = ops.FUSED4
+            wino[(1, g)] = ops.FUSED4
             dy = torch.randn(N, H, W, K, generator=gen).cuda()
             acc0 = torch.randn(N, H, W, C, generator=gen).cuda()
             rdx = torch.autograd.grad(ref, xd, dy.double().permute(0, 3, 1, 2))[0].permute(0, 2, 3, 1) + acc0.double()
@@ -343,10 +323,6 @@ def test_fused_winograd_f4_tile_parallel_kernel(hip, case):
                 xh = ((xb - mu) * isd).double().reshape(-1, C)
                 assert float((s2[0] - gq.sum(0)).abs().max() / gq.abs().sum(0).max()) <= 1e-6
                 assert float((s2[1] - (gq * xh).sum(0)).abs().max() / (gq * xh).abs().sum(0).max()) <= 1e-6
-    finally:
-        ops.AUTOTUNE = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
 
 
 @pytest.mark.parametrize("case", [(2, 16, 16, 64, 64), (3, 32, 48, 64, 128), (2, 20, 12, 128, 64), (1, 64, 64, 128, 256), (2, 2, 2, 64, 64),
@@ -368,10 +344,7 @@ def test_stride2_data_gradient_with_the_parity_classes_in_one_workgroup(hip, cas
     y = Fn.conv2d(xd, w.double().cpu().permute(0, 3, 1, 2), None, stride=2, padding=1)
     ref = torch.autograd.grad(y, xd, dy.double().cpu().permute(0, 3, 1, 2))[0].permute(0, 2, 3, 1).cuda()
     g = ops.conv_geom((N, H, W, C), w.shape, 2, 1, None)
-    saved = (ops.DGRAD_S2, ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED))
-    try:
-        ops._load_tuned_once()
-        ops.DGRAD_S2 = True
+    with ops.algorithms(DGRAD_S2=True):
         cache = {"train": True}
         with ops.LaunchTrace() as lt:
             dx = ops.conv_dgrad(dy, w, (N, H, W, C), stride=2, pad=1, cache=cache)
@@ -380,9 +353,8 @@ def test_stride2_data_gradient_with_the_parity_classes_in_one_workgroup(hip, cas
         dx1 = ops.conv_dgrad(dy, w, (N, H, W, C), add=acc0, stride=2, pad=1)
         r1 = ref + acc0.double()
         assert float((dx1.double() - r1).abs().max() / r1.abs().max()) <= 1e-5
-        ops.DGRAD_S2 = False
-        dxi = ops.conv_dgrad(dy, w, (N, H, W, C), add=acc0, stride=2, pad=1)
-        ops.DGRAD_S2 = True
+        with ops.switches(DGRAD_S2=False):
+            dxi = ops.conv_dgrad(dy, w, (N, H, W, C), add=acc0, stride=2, pad=1)
         assert float((dx1 - dxi).abs().max() / dxi.abs().max()) <= 5e-6
         xb = torch.randn(N, H, W, C, generator=gen).cuda()
         gam, bet = (torch.rand(C, generator=gen) + 0.5).cuda(), torch.randn(C, generator=gen).cuda()
@@ -402,12 +374,6 @@ def test_stride2_data_gradient_with_the_parity_classes_in_one_workgroup(hip, cas
             xh = ((xb - mu) * isd).double().reshape(-1, C)
             assert float((s2[0] - gq.sum(0)).abs().max() / gq.abs().sum(0).max()) <= 1e-6
             assert float((s2[1] - (gq * xh).sum(0)).abs().max() / (gq * xh).abs().sum(0).max()) <= 1e-6
-    finally:
-        ops.DGRAD_S2, ops.AUTOTUNE = saved[0], saved[1]
-        ops._WINO.clear()
-        ops._WINO.update(saved[2])
-        ops._TUNED.clear()
-        ops._TUNED.update(saved[3])
 
 
 @pytest.mark.parametrize("case", [(2, 24, 24, 1536, 1024), (1, 24, 24, 768, 512), (3, 8, 12, 512, 128)])
@@ -424,21 +390,17 @@ def test_opt_in_bf16_split_head_gemms(hip, case):
     dy = torch.randn(N, H, W, K, generator=g).cuda()
     x2, w2, dy2 = x.double().reshape(-1, C), w.double().reshape(K, C), dy.double().reshape(-1, K)
     ref = {"y": x2 @ w2.T + bias.double(), "dx": dy2 @ w2, "dw": dy2.T @ x2}
-    saved = ops.HEAD_BF16X3
-    try:
-        got = {}
-        for flag in (False, True):
-            ops.HEAD_BF16X3 = flag
+    got = {}
+    for flag in (False, True):
+        with ops.switches(HEAD_BF16X3=flag):
             got[flag] = {"y": ops.conv_fwd(x, w, bias=bias).reshape(-1, K), "dx": ops.conv_dgrad(dy, w, tuple(x.shape)).reshape(-1, C),
                          "dw": ops.conv_wgrad(x, dy, tuple(w.shape)).reshape(K, C)}
-        for k, r in ref.items():
-            s = float(r.abs().max())
-            e_exact = float((got[False][k].double() - r).abs().max()) / s
-            e_split = float((got[True][k].double() - r).abs().max()) / s
-            assert e_exact <= 5e-6 and e_split <= 2e-5, (k, e_exact, e_split)
-            assert not torch.equal(got[False][k], got[True][k])           # the flag really switches the arithmetic
-    finally:
-        ops.HEAD_BF16X3 = saved
+    for k, r in ref.items():
+        s = float(r.abs().max())
+        e_exact = float((got[False][k].double() - r).abs().max()) / s
+        e_split = float((got[True][k].double() - r).abs().max()) / s
+        assert e_exact <= 5e-6 and e_split <= 2e-5, (k, e_exact, e_split)
+        assert not torch.equal(got[False][k], got[True][k])           # the flag really switches the arithmetic
 
 
 @pytest.mark.parametrize("case", [(3, 20, 20, 128, 64), (2, 24, 36, 128, 192), (5, 16, 28, 256, 128), (1, 64, 64, 128, 128), (9, 32, 32, 256, 64), (3, 20, 28, 64, 256)])
@@ -609,9 +571,7 @@ def test_fused_winograd_f2_kernels_under_memory_pressure(hip):
     side = torch.cuda.Stream()
     big_a = torch.empty(1 << 27, device="cuda")
     big_b = torch.empty(1 << 27, device="cuda")
-    saved = (ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED))
-    try:
-        ops.AUTOTUNE = False
+    with ops.algorithms(AUTOTUNE=False) as wino:
         for it in range(24):
             N, H, W = rng.choice([8, 9, 17, 24, 40]), rng.choice([64, 96, 128]), rng.choice([64, 128, 144])
             g = torch.Generator().manual_seed(it)
@@ -622,7 +582,7 @@ def test_fused_winograd_f2_kernels_under_memory_pressure(hip):
             res = {}
             for algo in (0, ops.FUSED2):
                 for mode in range(3):
-                    ops._WINO[(mode, geom)] = algo
+                    wino[(mode, geom)] = algo
                 if algo and it % 2:
                     with torch.cuda.stream(side):
                         for _ in range(6):
@@ -633,10 +593,6 @@ def test_fused_winograd_f2_kernels_under_memory_pressure(hip):
             for k in range(3):
                 a, b = res[0][k], res[ops.FUSED2][k]
                 assert float((a - b).abs().max() / a.abs().max()) < 1e-5, (it, N, H, W, k)
-    finally:
-        ops.AUTOTUNE = saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(saved[1])
 
 
 @pytest.mark.parametrize("case", [(2, 32, 32, 64, 3, 2, 1), (3, 17, 23, 32, 3, 2, 1), (2, 16, 16, 128, 2, 2, 0), (1, 15, 15, 32, 3, 1, 1),
@@ -812,10 +768,8 @@ def test_data_gradient_pass_leaves_the_batch_norm_backward_sums(hip, path, relu,
     res = torch.randn(N, H, W, C, generator=g).cuda() if with_y else None
     y, sm, si = ops.bn_fwd_train(x, gamma, beta, rm, rs, relu=relu, res=res)
     geom = ops.conv_geom((N, H, W, C), w.shape, stride, pad, None)
-    saved = (dict(ops._WINO), ops.BWD_SUMS)
-    try:
-        ops.BWD_SUMS = 3
-        ops._WINO[(1, geom)] = {"wino4": 4, "wino2": 2, "fused64": ops.FUSED2}.get(path, 0)
+    with ops.algorithms(BWD_SUMS=3) as wino:
+        wino[(1, geom)] = {"wino4": 4, "wino2": 2, "fused64": ops.FUSED2}.get(path, 0)
         sums = ops.BnSums(x, y if (relu and with_y) else None, gamma, beta, sm, si, relu)
         cache = {}
         dz = ops.conv_dgrad(dy, w, (N, H, W, C), add=addt, stride=stride, pad=pad, cache=cache, sums=sums)
@@ -830,10 +784,6 @@ def test_data_gradient_pass_leaves_the_batch_norm_backward_sums(hip, path, relu,
         # the pieces == the one-call forms
         dx_ref, _, dg_ref, db_ref = ops.bn_bwd(x, yy, dz, gamma, sm, si, relu=relu, beta=beta)
         assert torch.equal(lb.materialise(), dx_ref)
-    finally:
-        ops._WINO.clear()
-        ops._WINO.update(saved[0])
-        ops.BWD_SUMS = saved[1]
 
 
 @pytest.mark.parametrize("case", [
@@ -859,36 +809,29 @@ def test_data_gradient_over_the_transposed_filter_is_bit_identical(hip, case):
     x = (torch.randn(N, H, W, C, generator=g) * 1.5 + 0.3).cuda()
     gamma, beta = (torch.rand(C, generator=g) + 0.5).cuda(), torch.randn(C, generator=g).cuda()
     y, sm, si = ops.bn_fwd_train(x, gamma, beta, torch.zeros(C).cuda(), torch.ones(C).cuda(), relu=True)
-    saved = (ops.DGRAD_T, ops.BWD_SUMS, dict(ops._WINO), ops.DGRAD_1X1T_GFLOP, ops.POLICY, ops.DGRAD_S2)
     out = {}
-    try:
-        ops.BWD_SUMS = 3
-        ops.DGRAD_1X1T_GFLOP = 0.0
-        ops.DGRAD_S2 = False                         # (the subject is the implicit-GEMM kernel's two filter layouts, also at stride 2)
-        ops.POLICY = lambda mode, geom: 0            # the direct kernels (no Winograd pass, nothing measured)
+    # DGRAD_S2 off: the subject is the implicit-GEMM kernel's two filter layouts, also at stride 2; the direct kernels (no Winograd
+    # pass, nothing measured)
+    with ops.algorithms(BWD_SUMS=3, DGRAD_1X1T_GFLOP=0.0, DGRAD_S2=False, POLICY=ops.direct_policy) as wino:
         for mode in ("plain", "transposed", "prepared"):
-            ops.DGRAD_T = mode != "plain"
-            ops._WINO.clear()
-            sums = ops.BnSums(x, None, gamma, beta, sm, si, True) if with_sums else None
-            cache = {"train": True}
-            if mode == "prepared":
-                cache["dgrad_t"] = True
-                ops.wino_prefetch_filters([(cache, w)])
-                assert cache["wt"][1]
-            dx = ops.conv_dgrad(dy, w, (N, H, W, C), add=addt, stride=stride, pad=pad, cache=cache, sums=sums)
-            assert ops._last_igemm_name().startswith("igemm_kernel<%d," % (1 if mode == "plain" else 3)), ops._last_igemm_name()
-            if mode == "prepared":
-                assert not cache["wt"][1]
-            if with_sums:
-                assert sums.partial is not None
-                la, _ = ops.bn_bwd_link(x, None, dx, gamma, sm, si, relu=True, beta=beta, pre=sums.partial)
-                out[mode] = (dx.clone(), la.coef.clone())
-            else:
-                out[mode] = (dx.clone(),)
-    finally:
-        ops.DGRAD_T, ops.BWD_SUMS, ops.DGRAD_1X1T_GFLOP, ops.POLICY, ops.DGRAD_S2 = saved[0], saved[1], saved[3], saved[4], saved[5]
-        ops._WINO.clear()
-        ops._WINO.update(saved[2])
+            wino.clear()
+            with ops.switches(DGRAD_T=mode != "plain"):
+                sums = ops.BnSums(x, None, gamma, beta, sm, si, True) if with_sums else None
+                cache = {"train": True}
+                if mode == "prepared":
+                    cache["dgrad_t"] = True
+                    ops.wino_prefetch_filters([(cache, w)])
+                    assert cache["wt"][1]
+                dx = ops.conv_dgrad(dy, w, (N, H, W, C), add=addt, stride=stride, pad=pad, cache=cache, sums=sums)
+                assert ops._last_igemm_name().startswith("igemm_kernel<%d," % (1 if mode == "plain" else 3)), ops._last_igemm_name()
+                if mode == "prepared":
+                    assert not cache["wt"][1]
+                if with_sums:
+                    assert sums.partial is not None
+                    la, _ = ops.bn_bwd_link(x, None, dx, gamma, sm, si, relu=True, beta=beta, pre=sums.partial)
+                    out[mode] = (dx.clone(), la.coef.clone())
+                else:
+                    out[mode] = (dx.clone(),)
     for mode in ("transposed", "prepared"):
         for a, b in zip(out[mode], out["plain"]):
             assert torch.equal(a, b), "%s: differs from denet_conv_dgrad" % mode
@@ -918,35 +861,27 @@ def test_data_gradient_of_a_1x1_layer_over_the_transposed_filter(hip, case):
     x = (torch.randn(N, H, W, C, generator=g) * 1.5 + 0.3).cuda()
     gamma, beta = (torch.rand(C, generator=g) + 0.5).cuda(), torch.randn(C, generator=g).cuda()
     y, sm, si = ops.bn_fwd_train(x, gamma, beta, torch.zeros(C).cuda(), torch.ones(C).cuda(), relu=True)
-    saved = (ops.DGRAD_1X1T_GFLOP, ops.BWD_SUMS, dict(ops._WINO), ops.DGRAD_T)
     out = {}
-    try:
-        ops.BWD_SUMS = 3
-        ops.DGRAD_T = False                 # "plain" = denet_conv_dgrad itself (the k-major filter reads)
+    with ops.algorithms(BWD_SUMS=3, DGRAD_T=False):          # DGRAD_T off: "plain" = denet_conv_dgrad itself (the k-major filter reads)
         for mode in ("plain", "transposed", "prepared"):
-            ops.DGRAD_1X1T_GFLOP = 0.0 if mode == "plain" else 1e-9
-            sums = ops.BnSums(x, None, gamma, beta, sm, si, True) if with_sums else None
-            cache = {"train": True}
-            if mode == "prepared":
-                cache["dgrad_1x1t"] = True
-                ops.wino_prefetch_filters([(cache, w)])
-                assert cache["wt"][1]
-            dx = ops.conv_dgrad(dy, w, (N, H, W, C), add=addt, stride=1, pad=0, cache=cache, sums=sums)
-            if mode != "plain":
-                assert cache.get("dgrad_1x1t")
-            if mode == "prepared":
-                assert not cache["wt"][1]                  # consumed: valid for one step
-            if with_sums:
-                assert sums.partial is not None
-                la, _ = ops.bn_bwd_link(x, None, dx, gamma, sm, si, relu=True, beta=beta, pre=sums.partial)
-                out[mode] = (dx.clone(), la.coef.clone())
-            else:
-                out[mode] = (dx.clone(),)
-    finally:
-        ops.DGRAD_1X1T_GFLOP, ops.BWD_SUMS = saved[:2]
-        ops.DGRAD_T = saved[3]
-        ops._WINO.clear()
-        ops._WINO.update(saved[2])
+            with ops.switches(DGRAD_1X1T_GFLOP=0.0 if mode == "plain" else 1e-9):
+                sums = ops.BnSums(x, None, gamma, beta, sm, si, True) if with_sums else None
+                cache = {"train": True}
+                if mode == "prepared":
+                    cache["dgrad_1x1t"] = True
+                    ops.wino_prefetch_filters([(cache, w)])
+                    assert cache["wt"][1]
+                dx = ops.conv_dgrad(dy, w, (N, H, W, C), add=addt, stride=1, pad=0, cache=cache, sums=sums)
+                if mode != "plain":
+                    assert cache.get("dgrad_1x1t")
+                if mode == "prepared":
+                    assert not cache["wt"][1]                  # consumed: valid for one step
+                if with_sums:
+                    assert sums.partial is not None
+                    la, _ = ops.bn_bwd_link(x, None, dx, gamma, sm, si, relu=True, beta=beta, pre=sums.partial)
+                    out[mode] = (dx.clone(), la.coef.clone())
+                else:
+                    out[mode] = (dx.clone(),)
     ref = torch.einsum("nhwk,kc->nhwc", dy.double(), w[:, 0, 0, :].double())
     if with_add:
         ref = ref + addt.double()
@@ -1424,9 +1359,7 @@ def test_conv_winograd_vs_direct(hip, shape, tile):
     dy = torch.randn(N, H, W, K, device="cuda", generator=g)
     addx = torch.randn(N, H, W, C, device="cuda", generator=g)
     tol = 2e-5 if tile == 2 else 1e-4
-    old = ops.AUTOTUNE
-    ops.AUTOTUNE = False
-    try:
+    with ops.switches(AUTOTUNE=False):
         ref = ops.conv_fwd(x, w, bias=bias, add=add, stride=1, pad=1)
         got = ops.conv_wino_fwd(x, w, bias=bias, add=add, tile=tile)
         assert float((ref - got).abs().max()) <= tol * float(ref.abs().max())
@@ -1439,5 +1372,3 @@ def test_conv_winograd_vs_direct(hip, shape, tile):
         rw = ops.conv_wgrad(x, dy, tuple(w.shape), stride=1, pad=1)
         gw = ops.conv_wino_wgrad(x, dy, tile=tile)
         assert float((rw - gw).abs().max()) <= 3 * tol * float(rw.abs().max())
-    finally:
-        ops.AUTOTUNE = old

@@ -124,13 +124,8 @@ def heuristic_kernels():
     """(name kept) the PRODUCT DEFAULT in this process too: committed decisions where the file has the geometry, ops.static_policy
     elsewhere, nothing measured - what the two worker processes run; the decision table is restored afterwards"""
     from denet_amd import ops
-    ops._load_tuned_once()
-    saved = (ops.AUTOTUNE, dict(ops._WINO), set(ops._TUNED), ops.MEASURE, ops.POLICY)
-    ops.AUTOTUNE, ops.MEASURE, ops.POLICY = True, False, None
-    yield
-    ops.AUTOTUNE, ops.MEASURE, ops.POLICY = saved[0], saved[3], saved[4]
-    ops._WINO.clear()
-    ops._WINO.update(saved[1])
+    with ops.algorithms(AUTOTUNE=True, MEASURE=False, POLICY=None):
+        yield
 
 
 def _replicas():

@@ -18,6 +18,7 @@ import torch.nn.functional as Fn
 
 from denet_amd import ops
 from denet_amd.model import model_cnn
+from fp64_model import build_model, png_dataset as _png_dataset, reference, rel as _rel
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BOUND = 1e-3
@@ -67,11 +68,6 @@ def ref_bwd(x, dy, size, stride, mode):
 def _clips(H, W, size, stride):
     OH, OW = ref_out(H, size[0], stride[0]), ref_out(W, size[1], stride[1])
     return (OH - 1) * stride[0] + size[0] > H, (OW - 1) * stride[1] + size[1] > W
-
-
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / np.abs(b).max())
 
 
 # name: (N, H, W, C, (kh, kw), (sh, sw))
@@ -212,10 +208,7 @@ def test_average_gradient_vs_fp64(hip, name):
 
 # ------------------------------------------------------------------------------------------------- through the layer
 def _model(desc, data_shape, B, CLS, seed):
-    np.random.seed(seed)
-    m = model_cnn.ModelCNN()
-    m.batch_size, m.class_num = B, CLS
-    m.build(desc, data_shape, "relu", "half", ["he-backward"])
+    m = build_model(desc, data_shape, B, CLS, seed=seed)
     m.class_labels = {"class%i" % i: i for i in range(CLS)}
     return m
 
@@ -241,11 +234,7 @@ def test_training_step_gradients_vs_fp64_autograd(hip):
     seen = conv.output.data[..., :32].double().cpu().numpy()
     _, most = ref_bwd(seen, np.zeros((B, 8, 8, 32)), pool.size, pool.stride, "max")
     assert most == 1
-    h = Fn.conv2d(torch.from_numpy(x).double(), w0.flip(2, 3), b0, stride=2, padding=3)
-    p = Fn.max_pool2d(h, 3, 2, padding=0, ceil_mode=True)
-    assert tuple(p.shape) == tuple(pool.output_shape)
-    logits = Fn.conv2d(p, w1.flip(2, 3))[:, :, 0, 0]
-    cost_ref = -torch.log_softmax(logits, dim=1)[torch.arange(B), torch.from_numpy(cls)].mean()
+    cost_ref, _, _ = reference(m, x, {id(conv): [w0, b0], id(head): [w1]}, cls, True)      # (asserts the pool's output shape)
     cost_ref.backward()
     print("cost", cost, float(cost_ref.detach()))
     assert abs(cost - float(cost_ref.detach())) <= BOUND * abs(float(cost_ref.detach()))
@@ -311,12 +300,7 @@ def test_average_border_layer_trains_and_predicts(hip):
     b0 = torch.from_numpy(conv.beta.get_value().copy()).double()
     cost, _ = m.train_step(x, [{"image_class": int(c)} for c in cls], 0, 0, 0.1, [0.9], 0.0)
 
-    def net(w0, b0, w1):
-        h = Fn.conv2d(torch.from_numpy(x).double(), w0.flip(2, 3), b0, padding=1)
-        p = Fn.avg_pool2d(h, 2, 2, padding=0, ceil_mode=True)
-        return Fn.conv2d(p, w1.flip(2, 3))[:, :, 0, 0]
-
-    cost_ref = -torch.log_softmax(net(w0, b0, w1), dim=1)[torch.arange(B), torch.from_numpy(cls)].mean()
+    cost_ref, _, _ = reference(m, x, {id(conv): [w0, b0], id(head): [w1]}, cls, True)
     cost_ref.backward()
     assert abs(cost - float(cost_ref.detach())) <= BOUND * abs(float(cost_ref.detach()))
     for l, t in ((conv, w0), (head, w1)):
@@ -324,23 +308,13 @@ def test_average_border_layer_trains_and_predicts(hip):
     pr = m.predict_output_step(x)
     with torch.no_grad():
         now = [torch.from_numpy(l.omega.get_value().copy()).double() for l in (conv, head)]
-        pr_ref = torch.softmax(net(now[0], torch.from_numpy(conv.beta.get_value().copy()).double(), now[1]), dim=1).numpy()
+        _, logits, _ = reference(m, x, {id(conv): [now[0], torch.from_numpy(conv.beta.get_value().copy()).double()],
+                                        id(head): [now[1]]}, cls, False)
+        pr_ref = torch.softmax(logits, dim=1).numpy()
     assert np.abs(pr - pr_ref).max() <= BOUND * pr_ref.max()
 
 
 # ------------------------------------------------------------------------------------------------- command line
-def _png_dataset(root, classes=3, per_class=4, seed=0):
-    from PIL import Image
-    rng = np.random.RandomState(seed)
-    for c in range(classes):
-        d = os.path.join(root, "class%i" % c)
-        os.makedirs(d)
-        for j in range(per_class):
-            img = rng.randint(0, 256, (32, 32, 3)).astype(np.uint8)
-            img[..., c] = 200 + 10 * (j % 5)
-            Image.fromarray(img).save(os.path.join(d, "img%i.png" % j))
-
-
 @pytest.mark.gpu
 def test_cli_predict_and_update_bn_on_a_border_keeping_model(hip, tmp_path):
     """model-predict (single mode), model-update-bn and model-modify --use-cudnn-pool on a saved `P.B` model and a folder of

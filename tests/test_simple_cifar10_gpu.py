@@ -18,15 +18,11 @@ import torch.nn.functional as Fn
 
 from denet_amd import ops
 from denet_amd.model import zoo
+from fp64_model import dropout_masks_of, param_layers, png_dataset as _png_dataset, reference, rel as _rel, relu_masks_of, sgd_step_errors
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rel(a, b):
-    a, b = a.double().cpu(), b.double().cpu()
-    return float((a - b).abs().max() / b.abs().max())
 
 
 def _true_conv_same(x, w):
@@ -78,13 +74,9 @@ def test_same_even_conv_vs_fp64(hip, k, N, H, C, K):
     assert float((part[1] - (yd * yd).sum(0)).abs().max() / (yd * yd).sum(0).max()) <= 1e-5
     # data gradient (the transposed-filter and the plain implicit-GEMM kernels)
     for dgrad_t in (True, False):
-        was = ops.DGRAD_T
-        ops.DGRAD_T = dgrad_t
-        try:
+        with ops.switches(DGRAD_T=dgrad_t):
             cache = {}
             dx = ops.conv_dgrad(dyn, wn, tuple(xn.shape), stride=1, pad=k // 2, cache=cache, ohw=(H, H))
-        finally:
-            ops.DGRAD_T = was
         assert cache["dgrad_tile"] == 0
         assert _rel(dx, xr.grad.permute(0, 2, 3, 1)) <= 1e-5
     # filter gradient (the device's taps are flipped)
@@ -161,78 +153,10 @@ def test_regression_probabilities_vs_fp64(hip, C, views):
 
 
 # ------------------------------------------------------------------------------------------------- one training step vs float64
-def _reference_forward(model, x, params, masks, cls, train=True, running=None, dtype=torch.float64, relu_masks=None, flips=None):
-    """zoo.simple_cifar10 in `dtype` on the host: params[i] = the reference-layout arrays of layer i (requires_grad), masks[i] =
-    the device's dropout mask of layer i (train). relu_masks[i] (train): the device's ReLU decisions of activation layer i, used
-    in place of the host's own; flips[i] receives the number of elements whose sign the two disagree on. Returns (cost, logits
-    at the centre, batch statistics per batch-norm layer)."""
-    h = torch.from_numpy(x).to(dtype)
-    stats = {}
-    for i, l in enumerate(model.layers[1:], start=1):
-        t = l.type_name
-        if t == "border":
-            b = l.border
-            h = Fn.pad(h, (b[0], b[1], b[2], b[3]))
-        elif t == "conv":
-            w = params[i][0]
-            if l.border_mode == "same":
-                h = _true_conv_same(h, w)
-            else:
-                assert l.border_mode == "valid"
-                h = Fn.conv2d(h, w.flip(2, 3))
-        elif t == "batchnorm":
-            gamma, beta = params[i]
-            if train:
-                mean = h.mean(dim=(0, 2, 3))
-                var = h.var(dim=(0, 2, 3), unbiased=False)
-                stats[i] = (mean.detach(), 1.0 / torch.sqrt(var.detach() + l.eps))
-                h = (h - mean[None, :, None, None]) / torch.sqrt(var + l.eps)[None, :, None, None]
-            else:
-                rm, rs = running[i]
-                inv = 1.0 / torch.sqrt((1.0 / rs) ** 2 + l.eps)          # batch_norm.py:50-52: eps twice
-                h = (h - rm[None, :, None, None]) * inv[None, :, None, None]
-            h = h * gamma[None, :, None, None] + beta[None, :, None, None]
-        elif t == "activation":
-            if relu_masks is None:
-                h = torch.relu(h)
-            else:
-                m = relu_masks[i].to(dtype)
-                if flips is not None:
-                    flips[i] = int(((h.detach() > 0).to(dtype) != m).sum())
-                h = h * m
-        elif t == "pool":
-            assert l.mode == "average_inc_pad"
-            h = Fn.avg_pool2d(h, l.size[0], l.stride[0])
-        elif t == "dropout":
-            if train:
-                h = h * masks[i]
-        elif t == "regression":
-            yc, xc = l.valid[0][1], l.valid[0][2]
-            logits = h[:, :, yc, xc]
-            lp = torch.log_softmax(logits, dim=1)
-            cost = -lp[torch.arange(len(cls)), torch.from_numpy(cls)].mean()
-            return cost, logits, stats
-        else:
-            raise AssertionError("unexpected layer " + t)
-
-
-class _policy:
+def _policy(name):
     """`direct`: every convolution pass on the direct kernels (exact fp32 FMA chains); `default`: what a training run uses
     (static_policy: Winograd on the 3x3 layers that take it)"""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        self.saved = (ops.POLICY, dict(ops._WINO))
-        if self.name == "direct":
-            ops._WINO.clear()
-            ops.POLICY = lambda mode, g: 0
-
-    def __exit__(self, *a):
-        ops.POLICY = self.saved[0]
-        ops._WINO.clear()
-        ops._WINO.update(self.saved[1])
+    return ops.algorithms(table={}, POLICY=ops.direct_policy) if name == "direct" else ops.algorithms()
 
 
 @pytest.mark.parametrize("policy", ["direct", "default"])
@@ -263,93 +187,59 @@ def _training_step_check(policy, seed):
     cls = rng.randint(0, CLS, B)
     metas = [{"image_class": int(c)} for c in cls]
     weights = set(id(p) for l in model.layers for p in l.weights())
-    before = {}
-    for i, l in enumerate(model.layers):
-        if l.type_name == "conv":
-            before[i] = [l.omega]
-        elif l.type_name == "batchnorm":
-            before[i] = [l.omega, l.beta]
-    values = {i: [p.get_value().copy() for p in ps] for i, ps in before.items()}
+    before = param_layers(model)
+    values = {id(l): [p.get_value().copy() for p in ps] for l, ps in before}
 
     cost, _ = model.train_step(x, metas, 0, 0, LR, [MOM], DECAY)
     torch.cuda.synchronize()
-    tiles = [(i, l._cache().get("fwd_tile"), l._cache().get("dgrad_tile")) for i, l in enumerate(model.layers) if l.type_name == "conv"]
+    tiles = [(l.layer_index, l._cache().get("fwd_tile"), l._cache().get("dgrad_tile")) for l in model.layers if l.type_name == "conv"]
     print(policy, "seed", seed, "algorithms (layer, forward, data gradient):", tiles)
     if policy == "direct":
         assert all(t[1] == 0 and t[2] in (0, None) for t in tiles), tiles
 
-    masks = {}
-    for i, l in enumerate(model.layers):
-        if l.type_name == "dropout":
-            assert l._seed is not None
-            n, c, hh, ww = l.input_shape
-            ones = torch.ones(n, hh, ww, l.input.cp, device="cuda")
-            m = ops.dropout(ones, c, l.dropout_rate, l._seed)[..., :c]
-            masks[i] = m.permute(0, 3, 1, 2).double().cpu()
-            assert 0.6 < float((masks[i] != 0).double().mean()) < 0.95
-    relu_masks = {}
-    for i, l in enumerate(model.layers):
-        if l.type_name == "activation":
-            d = l.output._data                     # the forward's activation (the solver changed gamma / beta since: no recompute)
-            assert d is not None, i
-            relu_masks[i] = (d[..., :l.output_shape[1]] > 0).permute(0, 3, 1, 2).cpu()
-    params = {i: [torch.from_numpy(v).double().requires_grad_(True) for v in vs] for i, vs in values.items()}
+    masks = dropout_masks_of(model)
+    assert len(masks) == 3
+    for m in masks.values():
+        assert 0.6 < float((m != 0).double().mean()) < 0.95
+    relu_masks = relu_masks_of(model)
+    params = {k: [torch.from_numpy(v).double().requires_grad_(True) for v in vs] for k, vs in values.items()}
     flips = {}
-    cost_ref, _, stats = _reference_forward(model, x, params, masks, cls, relu_masks=relu_masks, flips=flips)
+    cost_ref, _, stats = reference(model, x, params, cls, True, masks=masks, relu_masks=relu_masks, flips=flips)
     cost_ref.backward()
-    print(policy, "seed", seed, "ReLU decisions that differ from float64 (layer: count):", {i: n for i, n in flips.items() if n})
+    print(policy, "seed", seed, "ReLU decisions that differ from float64 (layer: count):",
+          {l.layer_index: flips[id(l)] for l in model.layers if flips.get(id(l))})
     assert abs(cost - float(cost_ref.detach())) <= 1e-3 * abs(float(cost_ref.detach())), (cost, float(cost_ref.detach()))
     bound = 1e-3
     report, bad = [], []
-    for i, ps in before.items():
-        for p, v, t in zip(ps, values[i], params[i]):
-            g_dev = torch.from_numpy(p.get_grad().copy()).double()     # (copies: a 1x1 filter's view may keep negative strides)
-            g_ref = t.grad
-            # SGD at iteration 0 (no momentum yet), L2 decay on the weights only
-            dec = DECAY if id(p) in weights else 0.0
-            v64 = torch.from_numpy(v).double()
-            p_ref = v64 - LR * (g_ref + dec * v64)
-            p_dev = torch.from_numpy(p.get_value().copy()).double()
-            e_g, e_p = _rel(g_dev, g_ref), _rel(p_dev - v64, p_ref - v64)
-            report.append("seed %d L%d %s: grad %.2e, update %.2e" % (seed, i, p.name, e_g, e_p))
-            if e_g > bound or e_p > bound:
-                bad.append(report[-1])
+    for l, p, e_g, e_p, _, _ in sgd_step_errors(before, values, params, weights, LR, DECAY):
+        report.append("seed %d L%d %s: grad %.2e, update %.2e" % (seed, l.layer_index, p.name, e_g, e_p))
+        if e_g > bound or e_p > bound:
+            bad.append(report[-1])
     print("%s seed %d: worst gradient %.2e, worst update %.2e" % (
         policy, seed, max(float(r.split("grad ")[1].split(",")[0]) for r in report),
         max(float(r.split("update ")[1]) for r in report)))
     assert not bad, bad
     # running statistics: momentum over (mean = 0, stdinv = 1) (batch_norm.py:75-76)
     running = {}
-    for i, l in enumerate(model.layers):
+    for l in model.layers:
         if l.type_name == "batchnorm":
             rm, rs = torch.from_numpy(l.mean.get_value().copy()).double(), torch.from_numpy(l.stdinv.get_value().copy()).double()
-            m_ref, s_ref = (1.0 - l.momentum) * stats[i][0], l.momentum + (1.0 - l.momentum) * stats[i][1]
-            assert _rel(rm, m_ref) <= 1e-3 and _rel(rs, s_ref) <= 1e-3, i
-            running[i] = (rm, rs)
+            m_ref = (1.0 - l.momentum) * stats[id(l)]["mean"]
+            s_ref = l.momentum + (1.0 - l.momentum) * stats[id(l)]["stdinv"]
+            assert _rel(rm, m_ref) <= 1e-3 and _rel(rs, s_ref) <= 1e-3, l.layer_index
+            running[id(l)] = (rm, rs)
 
     # test mode: the probabilities of the centre pixel with the updated parameters and statistics
     pr = model.predict_output_step(x)
-    now = {i: [torch.from_numpy(p.get_value().copy()).double() for p in ps] for i, ps in before.items()}
+    now = {id(l): [torch.from_numpy(p.get_value().copy()).double() for p in ps] for l, ps in before}
     with torch.no_grad():
-        _, logits, _ = _reference_forward(model, x, now, None, cls, train=False, running=running)
+        _, logits, _ = reference(model, x, now, cls, False, running=running)
     pr_ref = torch.softmax(logits, dim=1)
     assert pr.shape == (B, CLS)
     assert float((torch.from_numpy(pr).double() - pr_ref).abs().max()) <= 1e-3 * float(pr_ref.max())
 
 
 # ------------------------------------------------------------------------------------------------- command line
-def _png_dataset(root, classes=3, per_class=4, seed=0):
-    from PIL import Image
-    rng = np.random.RandomState(seed)
-    for c in range(classes):
-        d = os.path.join(root, "class%i" % c)
-        os.makedirs(d)
-        for j in range(per_class):
-            img = rng.randint(0, 256, (32, 32, 3)).astype(np.uint8)
-            img[..., c] = 200 + 10 * (j % 5)
-            Image.fromarray(img).save(os.path.join(d, "img%i.png" % j))
-
-
 def test_recipe_cli_train_then_predict(hip, tmp_path):
     train_dir, test_dir, out = str(tmp_path / "train"), str(tmp_path / "test"), tmp_path / "out"
     _png_dataset(train_dir, seed=1)

@@ -12,6 +12,7 @@ import torch
 from bf16_reference import bits, check_dgrad, check_fwd, check_wgrad, draw, ties
 from denet_amd import ops
 from denet_amd.model import audit, model_cnn, zoo
+from fp64_model import build_model, png_dataset as _png_dataset
 
 pytestmark = pytest.mark.gpu
 
@@ -150,12 +151,7 @@ STACK_B, STACK_IMG, STACK_CLASSES = 4, 16, 10
 
 
 def _build(desc, seed=5, solver="nesterov"):
-    np.random.seed(seed)
-    m = model_cnn.ModelCNN()
-    m.batch_size, m.class_num = STACK_B, STACK_CLASSES
-    m.build(desc, (3, STACK_IMG, STACK_IMG), "relu", "half", ["he-backward"])
-    head = m.layers[-2]
-    head.omega.set_value(head.omega.get_value() * 0.05)      # logits of order one: the softmax does not saturate
+    m = build_model(desc, (3, STACK_IMG, STACK_IMG), STACK_B, STACK_CLASSES, seed=seed, head_scale=0.05)
     m.build_train_func(solver)
     return m
 
@@ -286,11 +282,8 @@ def test_kernel_profile_names_and_counts_the_bf16_launches(hip):
     with ops.train_precision("bf16"):
         model.train_step(x, metas, 0, 0, 0.05, [0.9], 1e-4)
         prof = ops.KernelProfile()
-        ops.PROFILE = prof
-        try:
+        with ops.switches(PROFILE=prof):
             model.train_step(x, metas, 0, 1, 0.05, [0.9], 1e-4)
-        finally:
-            ops.PROFILE = None
         agg = prof.summary()
     assert agg[WGRAD + "<64, 128>"]["launches"] == 2 and agg[WGRAD + "<128, 128>"]["launches"] == 1, agg
     assert agg[COPY]["launches"] == 2 and agg[COPY]["flops"] == 0, agg
@@ -502,25 +495,13 @@ def test_it_trains(hip):
 
 
 # ---------------------------------------------------------------------------------------------------------- 4: the driver
-def _png_dataset(root, classes=2, per_class=4, seed=0):
-    from PIL import Image
-    rng = np.random.RandomState(seed)
-    for c in range(classes):
-        d = os.path.join(root, "class%i" % c)
-        os.makedirs(d)
-        for j in range(per_class):
-            img = rng.randint(0, 256, (32, 32, 3)).astype(np.uint8)
-            img[..., c] = 200 + 10 * (j % 5)
-            Image.fromarray(img).save(os.path.join(d, "img%i.png" % j))
-
-
 def test_model_train_with_precision_bf16(hip, tmp_path, monkeypatch):
     """two steps of `model-train --precision bf16 --test ...` on a folder dataset (in this process: the flag wraps the run), the
     epoch's test sweep on the model just trained, and a loadable model"""
     from denet_amd.model import train
     train_dir, test_dir, out = str(tmp_path / "train"), str(tmp_path / "test"), tmp_path / "out"
-    _png_dataset(train_dir, seed=1)
-    _png_dataset(test_dir, per_class=2, seed=2)      # (--test: the epoch ends with a test-mode sweep of the model just trained)
+    _png_dataset(train_dir, classes=2, seed=1)
+    _png_dataset(test_dir, classes=2, per_class=2, seed=2)      # (--test: the epoch ends with a test-mode sweep of the model just trained)
     out.mkdir()
     calls, w0 = [], ops.conv_wgrad_bf16
 
