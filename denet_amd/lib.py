@@ -167,6 +167,12 @@ SIGNATURES = {
     "denet_solver_step": (I, [P, P, P, L, L, F, F, I, F, F, I, P]),
     "denet_solver_adam": (I, [P, P, P, P, L, L, F, F, F, I, F, F, P]),
     "denet_scale": (I, [P, L, F, P]),
+    "denet_grad_norm_chunk_len": (I, []),
+    "denet_grad_norm_check_table": (I, [P, I, I, L]),
+    "denet_grad_norm_workspace_bytes": (Z, [I, I]),
+    "denet_grad_norm": (I, [P, P, I, I, F, F, P, P, P, P, P]),
+    "denet_solver_step_coef": (I, [P, P, P, L, L, F, F, I, F, F, I, P, P]),
+    "denet_solver_adam_coef": (I, [P, P, P, P, L, L, F, F, F, I, F, F, P, P]),
     "denet_corner_fwd": (I, [P, P] + [I] * 5 + [P]),
     "denet_loss_workspace_bytes": (Z, []),
     "denet_corner_loss": (I, [P] * 5 + [I] * 5 + [F, P]),

@@ -116,7 +116,8 @@ class ModelCNN:
         self.class_num = 0
         self.rng_seed = random.randint(1, 9999)
         layer_mod.set_rng_seed(self.rng_seed)
-        self.gradient_clip = 0.0
+        self.gradient_clip = 0.0   # > 0: every update is clipped to this global L2 norm; a training argument
+        self.track_grad_norm = False   # the norm pass without a limit: last_grad_norm / grad_norm_stats / param_norms
         self.skip_layer_updates = []
         self.bias_decay = False
         self.layers = []
@@ -124,6 +125,8 @@ class ModelCNN:
         self.input = None
         self.dist = None           # denet_amd.multi.DataParallel or None
         self._packed = False
+        self._norm = None          # ops.NormTable once packed
+        self._norm_ran = False
         self.timing = {}
 
     # ---------------------------------------------------------------- construction
@@ -283,6 +286,16 @@ class ModelCNN:
         self.cost_buf = torch.zeros(16, device="cuda")
         self._packed = True
         from .. import ops
+        # the norm pass (gradient clipping, gradient / weight norms): one segment per trained array over its 64-aligned extent,
+        # cut into chunks once; the small device buffers live with the table (ops.NormTable). Nothing here is launched by default
+        self.trained_params = weights + biases
+        self._norm = None
+        if self.trained_params:
+            self._norm = ops.NormTable([(self.param_ranges[id(p)][0], align(p.dev_size)) for p in self.trained_params],
+                                       self.n_trainable)
+            self._weight_norm = torch.zeros(self._norm.n_segments, device="cuda")
+            self._weight_norm_out = torch.zeros(2, device="cuda")
+        self._norm_ran = False
         ops.bump_weights_version()
 
     def build_train_func(self, solver_mode="sgd", cost_factors=[], use_acc_mode=False, skip_build=False):
@@ -311,8 +324,9 @@ class ModelCNN:
         assert len(self.cost_factors) == len(self.cost_layers), \
             "Different number of cost factors (%i) and cost layers (%i)" % (len(self.cost_factors), len(self.cost_layers))
         assert len(self.cost_layers) <= 8
-        if self.gradient_clip > 0.0:
-            raise NotImplementedError("gradient clipping is outside the hot path")
+        clip = float(self.gradient_clip)
+        if not math.isfinite(clip) or clip < 0.0:
+            raise ValueError("gradient_clip = %r: the limit of the global gradient norm is 0 (off) or a positive finite number" % (self.gradient_clip,))
         self.use_split_mode = False   # split points are identities here (288 GB of HBM)
         # `BN A` pairs whose batch-norm output nobody else reads run as the fused BN + ReLU (ActivationLayer; DENET_BN_ACT_FUSE=0: apart)
         for l in walk_layers(self.layers):
@@ -491,12 +505,85 @@ class ModelCNN:
         it, learn_rate, momentum, decay = acc["args"]
         n_decay = self.n_trainable if self.bias_decay else self.n_weights
         scale = 1.0 / acc["n"]
+        coef = self._norm_pass(acc["G"], scale)          # the one update clips the MEAN accumulated gradient
         ops.solver_step(self.P[:self.n_trainable], self.M[:self.n_trainable], acc["G"][:self.n_trainable], n_decay,
-                        float(learn_rate), float(momentum[0]), it, float(decay), SOLVER_MODES[self.solver_mode], scale)
+                        float(learn_rate), float(momentum[0]), it, float(decay), SOLVER_MODES[self.solver_mode], scale, coef=coef)
         self.S.copy_(acc["S"])
         ops.check(ops._L().denet_scale(self.S.data_ptr(), self.S.numel(), scale, ops.stream_ptr()), "scale")
         ops.bump_weights_version()
         self._acc = None
+
+    # ---- global-norm gradient clipping and gradient norms (csrc/grad_norm.hip). The reference's switch
+    # (model_cnn.py:237-239) clips the gradient arriving at the cost, i.e. scales by min(1, c), and is never set; here
+    # gradient_clip = c > 0 means: norm = |g| over every trained entry (after the solver's grad scale, before the decay term),
+    # the solver uses g * (c / norm if norm > c else 1). Norm and coefficient stay on the device; nothing is read back per step.
+    def _norm_pass(self, G, scale):
+        """right in front of the solver, on the compute stream: the norm pass over the trained part of G when a limit is set or
+        norms are tracked. Returns the coefficient's device tensor for the solver (a limit is set) or None (the plain solver)"""
+        clip = float(self.gradient_clip)
+        clip = clip if clip > 0.0 else 0.0
+        if not (clip > 0.0 or self.track_grad_norm) or self._norm is None:
+            return None
+        from .. import ops
+        ops.grad_norm(G, self._norm, scale, clip, stats=self._norm.stats)
+        self._norm_ran = True
+        return self._norm.coef if clip > 0.0 else None
+
+    def last_grad_norm(self):
+        """(norm, coef) of the last update. Synchronises: for tests and epoch ends, not for the step loop"""
+        assert self._packed and self._norm_ran, "no update has run the norm pass (gradient_clip > 0 or track_grad_norm)"
+        norm, coef = self._norm.out.cpu().tolist()
+        return norm, coef
+
+    def grad_norm_stats(self, reset=True):
+        """the device's running record since the last reset: {steps, clipped, nonfinite, mean, max, limit}; mean and max over the
+        steps with a finite norm. Synchronises"""
+        if not self._packed or self._norm is None:
+            return {"steps": 0, "clipped": 0, "nonfinite": 0, "mean": 0.0, "max": 0.0, "limit": float(self.gradient_clip)}
+        steps, clipped, nonfinite, total, largest = self._norm.stats.cpu().tolist()[:5]
+        if reset:
+            self._norm.stats.zero_()
+        finite = int(steps) - int(nonfinite)
+        return {"steps": int(steps), "clipped": int(clipped), "nonfinite": int(nonfinite), "mean": total / finite if finite else 0.0,
+                "max": largest, "limit": float(self.gradient_clip)}
+
+    def param_norms(self):
+        """one row per trained array: (layer_index, type_name, param name, gradient norm of the last update, weight norm). The
+        gradient norms are those the last norm pass left (0 if none ran); the weight norms come from one pass of the same kernel
+        over the parameter buffer, run here. Synchronises"""
+        from .. import ops
+        if not self._packed:
+            self.pack_device()
+        if self._norm is None:
+            return []
+        ops.grad_norm(self.P, self._norm, 1.0, 0.0, seg_norm=self._weight_norm, out=self._weight_norm_out)
+        wn = self._weight_norm.cpu().tolist()
+        gn = self._norm.seg_norm.cpu().tolist() if self._norm_ran else [0.0] * len(wn)
+        owner = {}
+        for l in walk_layers(self.layers):           # (a nested layer comes behind its container: the innermost owner stays)
+            for p in l.weights() + l.biases():
+                owner[id(p)] = l
+        rows = []
+        for p, g, w in zip(self.trained_params, gn, wn):
+            l = owner.get(id(p))
+            rows.append((getattr(l, "layer_index", -1), getattr(l, "type_name", "?"), p.name, g, w))
+        return rows
+
+    def grad_norm_log_lines(self, verbose=False):
+        """what the drivers log at an epoch's end ([] while neither a limit nor tracking is on); resets the record"""
+        if not (float(self.gradient_clip) > 0.0 or self.track_grad_norm) or not self._packed:
+            return []
+        st = self.grad_norm_stats(reset=True)
+        if st["steps"] == 0:
+            return []
+        line = "gradient norm: mean %.4g max %.4g, clipped %i of %i steps" % (st["mean"], st["max"], st["clipped"], st["steps"])
+        line += " (limit %g)" % st["limit"] if st["limit"] > 0.0 else " (no limit)"
+        if st["nonfinite"]:
+            line += ", %i non-finite steps" % st["nonfinite"]
+        lines = [line]
+        if verbose:
+            lines += ["  L%-3i %-16s %-8s grad %.4g weight %.4g" % row for row in self.param_norms()]
+        return lines
 
     def _device_step(self, epoch, it, learn_rate, momentum, decay, data_x, data_m, fetch_cost=True):
         from .. import ops
@@ -526,13 +613,15 @@ class ModelCNN:
             assert len(momentum) >= 2, "adam takes momentum = (beta1, beta2)"
             if getattr(self, "V", None) is None:
                 self.V = torch.zeros_like(self.M)       # second-moment accumulators (model_cnn.py:299)
+            coef = self._norm_pass(self.G, scale)
             ops.solver_adam(self.P[:self.n_trainable], self.M[:self.n_trainable], self.V[:self.n_trainable],
                             self.G[:self.n_trainable], n_decay, float(learn_rate), float(momentum[0]),
-                            float(momentum[1]), it, float(decay), scale)
+                            float(momentum[1]), it, float(decay), scale, coef=coef)
         else:
+            coef = self._norm_pass(self.G, scale)
             ops.solver_step(self.P[:self.n_trainable], self.M[:self.n_trainable], self.G[:self.n_trainable], n_decay,
                             float(learn_rate), float(momentum[0]), it, float(decay), SOLVER_MODES[self.solver_mode],
-                            scale)
+                            scale, coef=coef)
         ops.bump_weights_version()       # parameters and BN running statistics moved: inference caches are stale
         import torch
         if getattr(self, "input_consumed", None) is None:

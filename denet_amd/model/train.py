@@ -130,6 +130,13 @@ def build_parser(single=True):
                         help="arithmetic of the training convolutions: fp32 (the default, exact) or bf16 (opt-in: the eligible layers' "
                              "three passes with operands rounded to bf16 on the bf16 matrix cores, fp32 accumulation, fp32 master "
                              "weights and solver; outside the 1e-3 parity budget, DESIGN.md)")
+    parser.add_argument("--gradient-clip", type=float, default=0.0, metavar="NORM",
+                        help="opt-in: clip every update to this global L2 norm of the gradient (0 = off). This build's meaning of "
+                             "ModelCNN.gradient_clip, not the reference's never-set scaling by min(1, c) (DESIGN.md section 15); norm "
+                             "and coefficient stay on the device (csrc/grad_norm.hip)")
+    parser.add_argument("--gradient-norms", default=False, action="store_true",
+                        help="opt-in: track the global gradient norm of every update on the device and log it at every epoch's end, "
+                             "without clipping (at verbose level: the per-array gradient and weight norms too)")
     parser.add_argument("--model-desc", default=["C[100,7]", "P[2]", "C[150,4]", "P[2]", "C[250,4]", "P[2]", "C[300,1]", "R"],
                         nargs="+", type=str)
     return parser
@@ -164,11 +171,28 @@ def _default_log():
     return logging.info
 
 
+def set_gradient_norm_args(model, args, log=None):
+    """--gradient-clip / --gradient-norms -> the model's attributes (training arguments like the learning rate: not saved into
+    the .mdl.gz); build_train_func refuses a negative or non-finite limit"""
+    model.gradient_clip = float(getattr(args, "gradient_clip", 0.0) or 0.0)
+    model.track_grad_norm = bool(getattr(args, "gradient_norms", False))
+    if log is not None and model.gradient_clip > 0.0:
+        log("updates are clipped to a global gradient norm of %g (--gradient-clip)" % model.gradient_clip)
+
+
+def gradient_norm_lines(model, args):
+    """the epoch-end lines of the gradient-norm record ([] unless --gradient-clip / --gradient-norms); the per-array table with
+    --gradient-norms at verbose level"""
+    from ..common import logging
+    return model.grad_norm_log_lines(verbose=bool(getattr(args, "gradient_norms", False)) and logging.verbose_enabled())
+
+
 def train(args, train_data, log=None, test_data=None):
     """the epoch loop of train.py:117-151 (shuffle, train_epoch, learning-rate annealing, checkpoint per epoch)"""
     log = _default_log() if log is None else log
     model = model_cnn.initialize(args, train_data.get_data_shape(), train_data.class_labels, train_data.get_class_num())
     skip_train = getattr(args, "skip_train", False)
+    set_gradient_norm_args(model, args, log)
     if not skip_train:
         model.build_train_func(args.solver, args.cost_factors)
     learn_rate = args.learn_rate
@@ -196,6 +220,8 @@ def train(args, train_data, log=None, test_data=None):
                 cost = model.train_epoch(train_data, epoch, learn_rate, args.learn_momentum, args.learn_decay)
             costs.append(cost)
             log("epoch %i subset %i - cost: %.4f (lr %g)" % (epoch, subset, cost, learn_rate))
+        for line in gradient_norm_lines(model, args):
+            log("epoch %i %s" % (epoch, line))
         if len(args.learn_anneal_epochs) == 0 or (epoch + 1) in args.learn_anneal_epochs:
             learn_rate *= args.learn_anneal
         if test_data is not None and ((epoch % getattr(args, "test_epochs", 1)) == 0 or epoch == (args.epochs - 1)):

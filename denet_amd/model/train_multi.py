@@ -68,6 +68,9 @@ def train(args, train_data, dp, log=None):
     model = model_cnn.initialize(args, train_data.get_data_shape(), train_data.class_labels, train_data.get_class_num())
     factor = max(1, int(getattr(args, "batch_size_factor", 1)))
     use_acc_mode = factor > 1 and bool(getattr(args, "use_acc_mode", False))          # worker.py:60
+    # F = 1: every rank takes the norm of the same all-reduced gradient with a bit-reproducible kernel, so all ranks clip alike
+    # without communicating; F > 1: every local step (acc mode: the one update of train_end) clips its own gradient
+    train_mod.set_gradient_norm_args(model, args, log if dp is None or dp.rank == 0 else None)
     model.build_train_func(args.solver, args.cost_factors, use_acc_mode=use_acc_mode)
     if dp is not None:
         if factor == 1:
@@ -125,6 +128,9 @@ def train(args, train_data, dp, log=None):
                 log("epoch %i subset %i - cost (rank 0): %.4f (lr %g, %i GPUs)" % (epoch, subset, cost, learn_rate, world))
                 if getattr(args, "save_subsets", False) and not args.disable_intermediate:
                     model_cnn.save_to_file(model, args.output_prefix + "_epoch%03i_subset%03i.mdl.gz" % (epoch, subset + 1))
+        if rank == 0:
+            for line in train_mod.gradient_norm_lines(model, args):
+                log("epoch %i %s (rank 0)" % (epoch, line))
         if len(args.learn_anneal_epochs) == 0 or (epoch + 1) in args.learn_anneal_epochs:
             learn_rate *= args.learn_anneal
         if rank == 0 and (not args.disable_intermediate or epoch == args.epochs - 1):

@@ -59,7 +59,8 @@ def kernel_symbol(kind, a, b, c):
         return "conv_bf16_wgrad_kernel<%d, %d>" % (a, b)       # tile BM x BN of the opt-in bf16 filter gradient
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
              24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
-             33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel"}.get(kind)
+             33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel",
+             50: "grad_norm_partial_kernel", 51: "grad_norm_finish_kernel", 52: "solver_coef_kernel", 53: "adam_coef_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
 
@@ -2224,14 +2225,84 @@ def colsum(x, out=None):
     return out
 
 
-def solver_step(params, moments, grads, n_decay, lr, momentum, iteration, decay, mode, grad_scale=1.0):
+def solver_step(params, moments, grads, n_decay, lr, momentum, iteration, decay, mode, grad_scale=1.0, coef=None):
+    """coef: None (the plain kernel), or a one-element device tensor the kernel multiplies the scaled gradient by (grad_norm)"""
+    if coef is not None:
+        check(_L().denet_solver_step_coef(ptr(params), ptr(moments), ptr(grads), params.numel(), int(n_decay), lr, momentum,
+                                          int(iteration), decay, grad_scale, int(mode), ptr(coef), stream_ptr()), "solver_step_coef")
+        return
     check(_L().denet_solver_step(ptr(params), ptr(moments), ptr(grads), params.numel(), int(n_decay), lr, momentum,
                                  int(iteration), decay, grad_scale, int(mode), stream_ptr()), "solver_step")
 
 
-def solver_adam(params, m, v, grads, n_decay, lr, beta1, beta2, iteration, decay, grad_scale=1.0):
+def solver_adam(params, m, v, grads, n_decay, lr, beta1, beta2, iteration, decay, grad_scale=1.0, coef=None):
+    if coef is not None:
+        check(_L().denet_solver_adam_coef(ptr(params), ptr(m), ptr(v), ptr(grads), params.numel(), int(n_decay), lr, beta1, beta2,
+                                          int(iteration), decay, grad_scale, ptr(coef), stream_ptr()), "solver_adam_coef")
+        return
     check(_L().denet_solver_adam(ptr(params), ptr(m), ptr(v), ptr(grads), params.numel(), int(n_decay), lr, beta1, beta2,
                                  int(iteration), decay, grad_scale, stream_ptr()), "solver_adam")
+
+
+# ---- global-norm gradient clipping and gradient / weight norms (csrc/grad_norm.hip, DESIGN.md section 15): opt-in
+NORM_CHUNK = 8192            # floats per chunk of the reduction (denet_grad_norm_chunk_len(): a compile-time constant of the library)
+NORM_KERNELS = ("grad_norm_partial_kernel", "grad_norm_finish_kernel")      # what the norm pass adds to a step
+COEF_SOLVER_KERNELS = ("solver_coef_kernel", "adam_coef_kernel")            # the solvers that read its coefficient
+NORM_STATS = ("steps", "clipped", "nonfinite", "sum", "max")                # the first entries of the device's 8-double record
+
+
+def norm_chunks(ranges, chunk=NORM_CHUNK):
+    """ranges: [(offset, length)] in floats, one per array (= segment), ascending, 64-aligned. -> (table, first): table =
+    [(offset, length, segment)] with every range cut into chunks of at most `chunk` floats, first[s] = index of segment s's first
+    chunk (first[len(ranges)] = len(table)). Pure Python; the order of the table IS the order of the reduction"""
+    table, first, end = [], [], 0
+    for seg, (off, n) in enumerate(ranges):
+        off, n = int(off), int(n)
+        assert off % 64 == 0 and n % 64 == 0 and n > 0, "range %d (%d, %d) is not 64-aligned" % (seg, off, n)
+        assert off >= end, "range %d overlaps its predecessor" % seg
+        assert off + n < 2 ** 31, "offsets are 32-bit"
+        first.append(len(table))
+        for lo in range(off, off + n, chunk):
+            table.append((lo, min(chunk, off + n - lo), seg))
+        end = off + n
+    first.append(len(table))
+    return table, first
+
+
+class NormTable:
+    """the device copy of a chunk table with the small buffers of the norm pass: seg_norm [segments], out = {norm, coef}, stats
+    (8 doubles, kept across steps), the partials' workspace. Built once (ModelCNN.pack_device); n = floats of the buffers it is for"""
+
+    def __init__(self, ranges, n):
+        import numpy
+        table, self.first = norm_chunks(ranges)
+        self.n_chunks, self.n_segments, self.n = len(table), len(ranges), int(n)
+        host = numpy.ascontiguousarray(numpy.array(table, dtype=numpy.int32).reshape(-1, 3))
+        L = _L()
+        assert L.denet_grad_norm_chunk_len() == NORM_CHUNK
+        check(L.denet_grad_norm_check_table(host.ctypes.data, self.n_chunks, self.n_segments, self.n), "grad_norm_check_table")
+        self.bytes_read = 4 * sum(t[1] for t in table)
+        self.table = torch.from_numpy(host).cuda()
+        self.workspace = torch.zeros(int(L.denet_grad_norm_workspace_bytes(self.n_chunks, self.n_segments)), dtype=torch.uint8, device="cuda")
+        self.seg_norm = torch.zeros(self.n_segments, device="cuda")
+        self.out = torch.tensor([0.0, 1.0], device="cuda")
+        self.stats = torch.zeros(8, dtype=torch.float64, device="cuda")
+
+    @property
+    def coef(self):
+        return self.out[1:2]
+
+
+def grad_norm(x, nt, scale=1.0, clip=0.0, seg_norm=None, out=None, stats=None):
+    """two launches on the current stream: seg_norm[s] = scale * |x over segment s|, out = {norm, coef}; clip <= 0: norms only.
+    seg_norm / out default to the table's own buffers; stats: None or 8 doubles that the second launch updates"""
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() >= nt.n, (x.dtype, x.numel(), nt.n)
+    seg_norm = nt.seg_norm if seg_norm is None else seg_norm
+    out = nt.out if out is None else out
+    assert seg_norm.numel() >= nt.n_segments and out.numel() >= 2
+    check(_L().denet_grad_norm(ptr(x), ptr(nt.table), nt.n_chunks, nt.n_segments, float(scale), float(clip), ptr(nt.workspace),
+                               ptr(seg_norm), ptr(out), ptr(stats), stream_ptr()), "grad_norm")
+    return out
 
 
 def corner_fwd(conv, cn):

@@ -625,6 +625,34 @@ int denet_solver_adam(float* params, float* m, float* v, const float* grads, lon
                       float beta1, float beta2, int iteration, float decay, float grad_scale, hipStream_t stream);
 int denet_scale(float* x, long n, float s, hipStream_t stream);
 
+/* ---- OPT-IN global-norm gradient clipping and gradient / weight norms (csrc/grad_norm.hip; ModelCNN.gradient_clip and
+ *      track_grad_norm, model-train --gradient-clip / --gradient-norms). The reference's switch (denet/model/model_cnn.py:237-239,
+ *      theano.gradient.grad_clip on the cost) scales every gradient by min(1, c) and is never set: the definition here is this
+ *      build's. The default step makes none of these calls.
+ *   table         int [n_chunks][3] = (offset, length, segment) in floats: 64-aligned ranges of x cut into chunks of at most
+ *                 denet_grad_norm_chunk_len() floats, ascending, a segment's chunks consecutive, segments 0 .. n_segments-1 in order.
+ *                 grad_norm_check_table checks a HOST copy against these rules and the n floats of the buffer, without a device;
+ *                 grad_norm reads the DEVICE copy.
+ *   grad_norm     seg_norm[s] = scale * sqrt(sum of x^2 over segment s), out = {norm, coef}: norm = scale * sqrt(sum of x^2 over
+ *                 all chunks), coef = norm > clip ? clip / norm : 1 (clip <= 0: norms only, coef = 1; NaN gives 1, inf gives 0).
+ *                 stats (NULL or 8 doubles, kept across calls): steps | clipped | non-finite | sum of finite norms | largest finite
+ *                 norm. Products and sums in double in an order fixed by the table: bit-reproducible, no atomics. Two launches:
+ *                 grad_norm_partial_kernel (one workgroup per chunk), grad_norm_finish_kernel (one workgroup). workspace:
+ *                 denet_grad_norm_workspace_bytes(n_chunks, n_segments). Serves the weight norms too (x = the parameter buffer).
+ *   solver_*_coef denet_solver_step / denet_solver_adam with (g * grad_scale) * *coef in place of g * grad_scale; coef is a
+ *                 device pointer (out + 1 of grad_norm). *coef = 1 gives the bits of the plain entries.                        */
+int denet_grad_norm_chunk_len(void);
+int denet_grad_norm_check_table(const int* table, int n_chunks, int n_segments, long n);
+size_t denet_grad_norm_workspace_bytes(int n_chunks, int n_segments);
+int denet_grad_norm(const float* x, const int* table, int n_chunks, int n_segments, float scale, float clip, void* workspace,
+                    float* seg_norm, float* out, double* stats, hipStream_t stream);
+int denet_solver_step_coef(float* params, float* moments, const float* grads, long n, long n_decay, float lr,
+                           float momentum, int iteration, float decay, float grad_scale, int mode, const float* coef,
+                           hipStream_t stream);
+int denet_solver_adam_coef(float* params, float* m, float* v, const float* grads, long n, long n_decay, float lr,
+                           float beta1, float beta2, int iteration, float decay, float grad_scale, const float* coef,
+                           hipStream_t stream);
+
 /* ---- DeNet corner map  (denet/layer/denet_corner.py:50-53 log_softmax([x,-x]); :126-134 cost)
  *      conv:[B,H,W,CP] (first Cn channels are corner logits)  corner_pr/target:[B,2,Cn,H,W] (the reference's
  *      own layout, it is what build_samples consumes).  cost[0] receives cost_factor*corner_cost.         */
