@@ -21,6 +21,8 @@ from .. import ops
 
 TAP_THEANO = 0   # denet_sparse.py:72-84 (Theano CPU path, canonical per north star)
 TAP_CUDA = 1     # denet_sparse_op.py:65-71
+TAP_BILINEAR = 2  # opt-in, no reference counterpart (csrc/sparse_bilinear.hip): rule 0's coordinate, not rounded
+TAP_RULES = (TAP_THEANO, TAP_CUDA, TAP_BILINEAR)
 
 
 from .roi_handoff import (PyRandomMirror, py_random_doubles, RoiHandoff)      # noqa: F401 (re-exported)
@@ -34,7 +36,7 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
     log_coverage = False
 
     def __init__(self, layers, grid_size=3, sample_num=16, corner_threshold=0.01, random_sample=0.0, local_max=0,
-                 nms_threshold=0.7, sample_gt=True, version="v2", json_param={}):
+                 nms_threshold=0.7, sample_gt=True, version="v2", json_param={}, tap_rule=TAP_THEANO):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -48,7 +50,10 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         self.random_sample = json_param.get("randomSample", random_sample)
         self.local_max = json_param.get("localMax", local_max)
         self.version = json_param.get("version", version)
-        self.tap_rule = json_param.get("tapRule", TAP_THEANO)
+        self.tap_rule = json_param.get("tapRule", tap_rule)
+        if isinstance(self.tap_rule, bool) or self.tap_rule not in TAP_RULES:
+            raise ValueError("denet-sparse: tapRule must be 0 (theano), 1 (cuda) or 2 (bilinear), got %r" % (self.tap_rule,))
+        self.tap_rule = int(self.tap_rule)
 
         self.corner_max = 1024
         self.thread_num = self.batch_size
@@ -99,8 +104,10 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
     def parse_desc(layers, name, tags, params):
         if name != "DNS":
             return False
+        # tag I (this build's own): bilinear taps. Without it the constructor is called exactly as the reference calls its own
+        extra = {"tap_rule": TAP_BILINEAR} if "I" in tags else {}
         layers.append(DeNetSparseLayer(layers, params.get(0, 3), params.get(1, 4), params.get(2, 0.01),
-                                       params.get(3, 0.1), params.get(4, 0), params.get(5, 1.0), not "G" in tags))
+                                       params.get(3, 0.1), params.get(4, 0), params.get(5, 1.0), not "G" in tags, **extra))
         return True
 
     # ---- reference list-of-tuples view --------------------------------------------------------------------
@@ -160,7 +167,7 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         # everything the hand-off can settle without the proposal is settled BEFORE the wait (the device stands idle from the
         # moment the copy lands until the gather is queued): the checks of the short forms, the gather's output buffers
         ready = self._short_handoff_ready() if raw_only else None
-        if raw_only and get_train():
+        if raw_only and get_train() and self.tap_rule != TAP_BILINEAR:
             self._gather_pre = ops.sparse_fwd_buffers(self.batch_size * self.sample_count, self.grid_size, self.output.cp)
         # ... and while it waits (the device is a whole backbone behind), the host repeats a dry run of the fast form's native call
         # every quarter of a millisecond: the call finds its code, tables and the generator stretch in cache when the proposal lands
@@ -453,6 +460,8 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         json.update({"gridSize": self.grid_size, "sampleNum": self.sample_num, "sampleGT": self.sample_gt,
                      "localMax": self.local_max, "cornerThreshold": self.corner_threshold,
                      "randomSample": self.random_sample, "nmsThreshold": self.nms_threshold, "version": self.version})
+        if self.tap_rule != TAP_THEANO:      # (a default layer's dictionary stays the reference's, key for key)
+            json["tapRule"] = self.tap_rule
         return json
 
     # ---- execution ----------------------------------------------------------------------------------------
@@ -467,13 +476,21 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         else:
             fmap, coff, F = cl.sample_shared, cl.corner_num, cl.sample_feat
         assert self.sample_bbox is not None, "set_samples() must run before the sparse layer"
-        out, self._taps = ops.sparse_fwd(fmap, self.sample_bbox, coff, F, self.sample_count, self.grid_size,
-                                         self.output.cp, self.tap_rule, buffers=self.__dict__.pop("_gather_pre", None))
-        self.output.data = out.view(self.batch_size, self.sample_num, self.sample_num, self.output.cp)
+        side_sort = get_train() and os.environ.get("DENET_SIDE_SORT", "1") == "1"
+        fm = fmap.shape
         self._sorted_ev = None
-        if get_train() and os.environ.get("DENET_SIDE_SORT", "1") == "1":
-            fm = fmap.shape
-            self._sorted_ev = ops.sparse_sort_async(self._taps, fm[0], fm[1], fm[2], self.sample_count, self.grid_size)
+        if self.tap_rule == TAP_BILINEAR:
+            self.__dict__.pop("_gather_pre", None)           # (the nearest rules' buffers: this rule keeps four cells and weights per tap)
+            out, self._taps, self._wts = ops.sparse_bilinear_fwd(fmap, self.sample_bbox, coff, F, self.sample_count, self.grid_size,
+                                                                 self.output.cp, keep=get_train())
+            if side_sort:
+                self._sorted_ev = ops.sparse_bilinear_sort_async(self._taps, fm[0], fm[1], fm[2], self.sample_count, self.grid_size)
+        else:
+            out, self._taps = ops.sparse_fwd(fmap, self.sample_bbox, coff, F, self.sample_count, self.grid_size,
+                                             self.output.cp, self.tap_rule, buffers=self.__dict__.pop("_gather_pre", None))
+            if side_sort:
+                self._sorted_ev = ops.sparse_sort_async(self._taps, fm[0], fm[1], fm[2], self.sample_count, self.grid_size)
+        self.output.data = out.view(self.batch_size, self.sample_num, self.sample_num, self.output.cp)
         mirror = self.__dict__.pop("_pending_push", None)
         if mirror is not None:
             mirror.push()
@@ -482,5 +499,9 @@ class DeNetSparseLayer(RoiHandoff, AbstractLayer):
         cl = self.corner_layer
         dconv = cl.alloc_dconv(zero=False)
         dy = self.output.grad.view(-1, self.output.cp)
+        if self.tap_rule == TAP_BILINEAR:
+            ops.sparse_bilinear_bwd(dy, self._taps, self._wts, dconv, cl.corner_num, cl.sample_feat, self.sample_count, self.grid_size,
+                                    cl.corner_num + cl.sample_feat, presorted=getattr(self, "_sorted_ev", None))
+            return
         ops.sparse_bwd(dy, self._taps, dconv, cl.corner_num, cl.sample_feat, self.sample_count, self.grid_size,
                        cl.corner_num + cl.sample_feat, presorted=getattr(self, "_sorted_ev", None))

@@ -181,6 +181,10 @@ SIGNATURES = {
     "denet_sparse_sort_is_single": (I, [I] * 5),
     "denet_sparse_sort": (I, [P, P, Z] + [I] * 5 + [P]),
     "denet_sparse_bwd": (I, [P, P, P, Z, P] + [I] * 10 + [P]),
+    "denet_sparse_bilinear_fwd": (I, [P] * 5 + [I] * 9 + [P]),
+    "denet_sparse_bilinear_workspace_bytes": (Z, [I] * 5),
+    "denet_sparse_bilinear_sort": (I, [P, P, Z] + [I] * 5 + [P]),
+    "denet_sparse_bilinear_bwd": (I, [P, P, P, P, Z, P] + [I] * 10 + [P]),
     "denet_detect_loss": (I, [P] * 9 + [I] * 6 + [F, F, F, I, P]),
     "denet_detect_decode": (I, [P] * 5 + [I] * 6 + [F, P]),
     "denet_detect_nms": (I, [P] * 5 + [I, I, I, F, F, P]),

@@ -60,7 +60,8 @@ def kernel_symbol(kind, a, b, c):
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
              24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
              33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel",
-             50: "grad_norm_partial_kernel", 51: "grad_norm_finish_kernel", 52: "solver_coef_kernel", 53: "adam_coef_kernel"}.get(kind)
+             50: "grad_norm_partial_kernel", 51: "grad_norm_finish_kernel", 52: "solver_coef_kernel", 53: "adam_coef_kernel",
+             60: "sparse_bilinear_fwd_kernel", 61: "sparse_bilinear_bwd_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
 
@@ -2373,6 +2374,63 @@ def sparse_bwd(dy, taps, dfmap, coff, F, rois_per_image, gs, zero_from, presorte
         torch.cuda.current_stream().wait_event(presorted)
     check(_L().denet_sparse_bwd(ptr(dy), None if presorted is not None else ptr(taps), ptr(ws), ws.numel(), ptr(dfmap), B, H, W, CP,
                                 coff, F, rois_per_image, gs, kp, zero_from, stream_ptr()), "sparse_bwd")
+    return dfmap
+
+
+# ---- opt-in bilinear RoI sampling (tapRule 2, `DNS.I`; csrc/sparse_bilinear.hip) --------------------------
+def sparse_bilinear_fwd(fmap, bbox, coff, F, rois_per_image, gs, kp, keep=True):
+    """-> (out [M, kp], taps4 [M, gs*gs*4] int32 cells, wts4 [M, gs*gs*4] fp32 weights); keep=False (inference): no tap or weight
+    arrays are made, (out, None, None)"""
+    B, H, W, CP = fmap.shape
+    M = B * rois_per_image
+    out = empty(M, kp)
+    taps4 = torch.empty((M, gs * gs * 4), dtype=torch.int32, device="cuda") if keep else None
+    wts4 = torch.empty((M, gs * gs * 4), dtype=torch.float32, device="cuda") if keep else None
+    check(_L().denet_sparse_bilinear_fwd(ptr(fmap), ptr(bbox), ptr(out), ptr(taps4), ptr(wts4), B, H, W, CP, coff, F, rois_per_image,
+                                         gs, kp, stream_ptr()), "sparse_bilinear_fwd")
+    return out, taps4, wts4
+
+
+def _sparse_bilinear_ws(B, H, W, rois_per_image, gs):
+    """the grouping's workspace under a key of its own: the default path's buffer is never resized by this mode"""
+    nbytes = _L().denet_sparse_bilinear_workspace_bytes(B, H, W, rois_per_image, gs)
+    if nbytes == 0:
+        raise _lib.DenetHipError("sparse_bilinear: a feature map of %d x %d cells with %d RoIs per image has no grouping "
+                            "(at most 32768 cells)" % (H, W, rois_per_image))
+    return WS.get("sparse_bilinear_sort", nbytes)
+
+
+def sparse_bilinear_sort_async(taps4, B, H, W, rois_per_image, gs):
+    """sparse_sort_async for the expanded slot list of the bilinear rule (four slots per tap): the one-kernel form stays on the
+    compute stream, the three-kernel form goes to the side stream; returns the event sparse_bilinear_bwd(presorted=...) waits for"""
+    global _SORT_STREAM
+    if _SORT_STREAM is None:
+        init_streams()
+    ws = _sparse_bilinear_ws(B, H, W, rois_per_image, gs)
+    if bool(_L().denet_sparse_sort_is_single(B, H, W, rois_per_image * 4, gs)):
+        check(_L().denet_sparse_bilinear_sort(ptr(taps4), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()),
+              "sparse_bilinear_sort")
+        ev = torch.cuda.Event()
+        ev.record()
+        return ev
+    _SORT_STREAM.wait_stream(torch.cuda.current_stream())          # taps4 is written by sparse_bilinear_fwd on this stream
+    with torch.cuda.stream(_SORT_STREAM):
+        check(_L().denet_sparse_bilinear_sort(ptr(taps4), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()),
+              "sparse_bilinear_sort")
+        ev = torch.cuda.Event()
+        ev.record(_SORT_STREAM)
+    return ev
+
+
+def sparse_bilinear_bwd(dy, taps4, wts4, dfmap, coff, F, rois_per_image, gs, zero_from, presorted=None):
+    B, H, W, CP = dfmap.shape
+    kp = dy.shape[-1]
+    ws = _sparse_bilinear_ws(B, H, W, rois_per_image, gs)
+    if presorted is not None:
+        torch.cuda.current_stream().wait_event(presorted)
+    check(_L().denet_sparse_bilinear_bwd(ptr(dy), None if presorted is not None else ptr(taps4), ptr(wts4), ptr(ws), ws.numel(),
+                                         ptr(dfmap), B, H, W, CP, coff, F, rois_per_image, gs, kp, zero_from, stream_ptr()),
+          "sparse_bilinear_bwd")
     return dfmap
 
 

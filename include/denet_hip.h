@@ -31,6 +31,7 @@ typedef struct ihipStream_t* hipStream_t;
 #define DENET_ERR_ARG (-1000)
 #define DENET_TAP_THEANO 0 /* denet/layer/denet_sparse.py:72-84  (i*extent)/(gs-1), round half to even */
 #define DENET_TAP_CUDA 1   /* denet/layer/denet_sparse_op.py:65-71 i*extent*(1/(gs-1)), lroundf           */
+#define DENET_TAP_BILINEAR 2 /* no reference counterpart: rule 0's coordinate, not rounded */
 #define DENET_ACT_SIGMOID 1  /* denet/layer/activation.py:28-29 */
 #define DENET_ACT_TANH 2     /* denet/layer/activation.py:37-38 */
 #define DENET_ACT_ELU 3      /* denet/layer/activation.py:35-36 (alpha = 1) */
@@ -682,6 +683,29 @@ int denet_sparse_sort(const int* taps, void* sort_ws, size_t sort_ws_bytes, int 
 int denet_sparse_bwd(const float* dy, const int* taps, void* sort_ws, size_t sort_ws_bytes, float* dfmap, int B, int H,
                      int W, int CP, int coff, int F, int rois_per_image, int gs, int KP, int zero_from,
                      hipStream_t stream);
+
+/* ---- bilinear RoI sampling, opt-in (tapRule 2, `DNS.I`; csrc/sparse_bilinear.hip). The reference has no counterpart - it reads
+ *      every tap from the nearest cell; the definition is DESIGN.md section 16. Arguments as in the sparse sampling above.
+ *      A tap reads its four surrounding cells (y0,x0), (y0,x1), (y1,x0), (y1,x1) = corner q 0..3; taps4:[B*rois,gs*gs*4] int32
+ *      receives the cells and wts4:[B*rois,gs*gs*4] the fp32 weights (both NULL in inference: nothing is kept).             */
+int denet_sparse_bilinear_fwd(const float* fmap, const float* bbox, float* out, int* taps4, float* wts4, int B, int H, int W,
+                              int CP, int coff, int F, int rois_per_image, int gs, int KP, hipStream_t stream);
+/* bytes of the grouping's workspace: the sort workspace of the nearest rules for the expanded list of 4 * rois_per_image * gs * gs
+ * slots per image, s' = (roi * gs*gs + tap) * 4 + q; 0 for a refused geometry (H*W > 32768 cells). The reference has no
+ * counterpart. */
+size_t denet_sparse_bilinear_workspace_bytes(int B, int H, int W, int rois_per_image, int gs);
+/* groups the expanded slot list by cell, every cell's slots in ascending order (the counting sort of the nearest rules, handed
+ * 4 * rois_per_image: one kernel up to 65535 slots per image and 4096 cells, else three); depends only on taps4. The reference
+ * has no counterpart. */
+int denet_sparse_bilinear_sort(const int* taps4, void* sort_ws, size_t sort_ws_bytes, int B, int H, int W, int rois_per_image,
+                               int gs, hipStream_t stream);
+/* gradient with respect to the feature map: a cell = sum over its slots, in ascending slot order, of wts4[s'] * dy row (s' >> 2);
+ * write contract of the nearest rules' gradient (channels [coff, coff+F) overwritten, zero_from.. zeroed, below coff untouched).
+ * taps4 == NULL: sort_ws already holds the lists of the bilinear sort. Refused with a message: F not a multiple of 4, F > 256,
+ * CP / KP not multiples of 4, H*W > 32768. The reference has no counterpart. */
+int denet_sparse_bilinear_bwd(const float* dy, const int* taps4, const float* wts4, void* sort_ws, size_t sort_ws_bytes,
+                              float* dfmap, int B, int H, int W, int CP, int coff, int F, int rois_per_image, int gs, int KP,
+                              int zero_from, hipStream_t stream);
 
 /* ---- detection cost  (denet/layer/denet_detect.py:238-313 get_errors/cost; theano_util.py:27-34)
  *      logits:[M,CP] (ncls class logits, nreg box regressors, nfit independent-fitness logits); det_target:[M,ncls];
