@@ -48,6 +48,26 @@ def round_up(v, m):
     return ((int(v) + m - 1) // m) * m
 
 
+def focal_gamma_value(type_name, value):
+    """the focalGamma of a cost layer (opt-in focal cost) as a float: 0 (off) or finite and >= 1; the
+    (1 - p)^(gamma - 1) factor of the gradient is singular for 0 < gamma < 1"""
+    import math
+    ok = isinstance(value, (int, float)) and not isinstance(value, bool)
+    if ok:
+        value = float(value)
+        ok = value == 0.0 or (math.isfinite(value) and value >= 1.0)
+    if not ok:
+        raise ValueError("%s: focalGamma must be 0 (plain cost) or a finite number >= 1, got %r" % (type_name, value))
+    return value
+
+
+def focal_log_lines(model):
+    """one line per cost layer that runs the focal cost (focal_gamma > 0), for the training drivers' start-up log"""
+    from ..model.model_cnn import walk_layers
+    return ["%s layer %d: focal gamma %g (the cost is not renormalised: raise costFactor to compensate)" %
+            (l.type_name, l.layer_index, l.focal_gamma) for l in walk_layers(model.layers) if getattr(l, "focal_gamma", 0.0) > 0.0]
+
+
 class Act:
     """Static activation handle: what `layer.output` is in this build.
 

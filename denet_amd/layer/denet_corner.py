@@ -4,7 +4,7 @@ bias +5 (:41-47), corner_pr = log_softmax([x,-x]) over a new axis (:50-53), host
 (get_target :81-123) and the corner NLL cost (:126-134). The layer passes its input through."""
 import numpy
 
-from . import AbstractLayer, InitialLayer
+from . import AbstractLayer, InitialLayer, focal_gamma_value
 from .convolution import ConvLayer
 from .. import ops
 
@@ -12,7 +12,7 @@ from .. import ops
 class DeNetCornerLayer(AbstractLayer):
     type_name = "denet-corner"
 
-    def __init__(self, layers, sample_feat=512, cost_factor=1, dropout=0.0, use_center=False, json_param={}):
+    def __init__(self, layers, sample_feat=512, cost_factor=1, dropout=0.0, use_center=False, json_param={}, focal_gamma=0.0):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -24,6 +24,8 @@ class DeNetCornerLayer(AbstractLayer):
         self.cost_factor = json_param.get("costFactor", cost_factor)
         self.use_center = json_param.get("useCenter", use_center)
         self.dropout = json_param.get("dropout", dropout)
+        # opt-in focal cost, no reference counterpart (csrc/focal.hip); 0 = the reference's plain cost
+        self.focal_gamma = focal_gamma_value(self.type_name, json_param.get("focalGamma", focal_gamma))
 
         self.corner_num = 5 if self.use_center else 4
         self.layers = [InitialLayer(self.input, self.input_shape)]
@@ -50,13 +52,17 @@ class DeNetCornerLayer(AbstractLayer):
     def parse_desc(layers, name, tags, params):
         if name != "DNC":
             return False
-        layers.append(DeNetCornerLayer(layers, params.get(0, 512), params.get(1, 1.0), params.get(2, 0.0), "C" in tags))
+        # fourth parameter (this build's own): focal gamma. Without it the constructor is called exactly as the reference calls its own
+        extra = {"focal_gamma": params.get(3)} if 3 in params else {}
+        layers.append(DeNetCornerLayer(layers, params.get(0, 512), params.get(1, 1.0), params.get(2, 0.0), "C" in tags, **extra))
         return True
 
     def export_json(self):
         json = super().export_json()
         json.update({"sampleFeat": self.sample_feat, "useCenter": self.use_center, "costFactor": self.cost_factor,
                      "dropout": self.dropout})
+        if self.focal_gamma != 0.0:          # (a default layer's dictionary stays the reference's, key for key)
+            json["focalGamma"] = self.focal_gamma
         return json
 
     def get_target(self, model, samples, metas):
@@ -145,6 +151,9 @@ class DeNetCornerLayer(AbstractLayer):
             # if no RoI gather follows, the sampling / padding channels carry no gradient: start from zeros
             dconv = self.alloc_dconv(zero=not ctx.has_sparse)
         ops.wait_upload(getattr(self, "_target_ev", None))
+        if self.focal_gamma > 0.0:
+            ops.corner_loss_focal(self.corner_pr, self._target, dconv, cost_out, float(self.cost_factor), self.focal_gamma)
+            return
         ops.corner_loss(self.corner_pr, self._target, dconv, cost_out, float(self.cost_factor))
 
     def backward(self, ctx):

@@ -7,7 +7,7 @@ import os
 
 import numpy
 
-from . import AbstractLayer, InitialLayer
+from . import AbstractLayer, InitialLayer, focal_gamma_value
 from .convolution import ConvLayer
 from .. import common
 from .. import ops
@@ -17,7 +17,7 @@ class DeNetDetectLayer(AbstractLayer):
     type_name = "denet-detect"
 
     def __init__(self, layers, class_num=10, overlap_threshold=0.5, cost_factor=1.0, bbox_factor=0.0, indfit_factor=0.0,
-                 use_jointfit=False, use_bounded_iou=False, json_param={}):
+                 use_jointfit=False, use_bounded_iou=False, json_param={}, focal_gamma=0.0):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -32,6 +32,8 @@ class DeNetDetectLayer(AbstractLayer):
         self.use_bounded_iou = json_param.get("useBoundedIoU", use_bounded_iou)
         self.indfit_factor = json_param.get("fitnessFactor", indfit_factor)
         self.use_indfit = (self.indfit_factor > 0.0)
+        # opt-in focal class cost, no reference counterpart (csrc/focal.hip); 0 = the reference's plain cost
+        self.focal_gamma = focal_gamma_value(self.type_name, json_param.get("focalGamma", focal_gamma))
         assert not (self.use_indfit and self.use_jointfit), "Cannot enable both fitness methods at once!"
 
         self.sparse_layer = common.find_layers(layers, "denet-sparse", False)
@@ -70,8 +72,10 @@ class DeNetDetectLayer(AbstractLayer):
     def parse_desc(layers, name, tags, params):
         if name != "DND":
             return False
+        # fifth parameter (this build's own): focal gamma. Without it the constructor is called exactly as the reference calls its own
+        extra = {"focal_gamma": params.get(4)} if 4 in params else {}
         layers.append(DeNetDetectLayer(layers, params.get("classNum"), params.get(0, 0.5), params.get(1, 1.0),
-                                       params.get(2, 0.0), params.get(3, 0.0), "J" in tags, "B" in tags))
+                                       params.get(2, 0.0), params.get(3, 0.0), "J" in tags, "B" in tags, **extra))
         return True
 
     def import_json(self, json_param):
@@ -84,6 +88,8 @@ class DeNetDetectLayer(AbstractLayer):
         json.update({"costFactor": self.cost_factor, "bboxFactor": self.bbox_factor, "fitnessFactor": self.indfit_factor,
                      "useJointFitness": self.use_jointfit, "useBoundedIoU": self.use_bounded_iou,
                      "classNum": self.class_num, "overlapThreshold": self.overlap_threshold})
+        if self.focal_gamma != 0.0:          # (a default layer's dictionary stays the reference's, key for key)
+            json["focalGamma"] = self.focal_gamma
         return json
 
     def _buf(self, name, shape):
@@ -276,10 +282,16 @@ class DeNetDetectLayer(AbstractLayer):
         dl = ops.empty(M, self.conv.kp) if want_grad else None
         t = self._targets
         ops.wait_upload(t.get("event"))
-        ops.detect_loss(lg, t["det"], t["valid"], t["reg"], self.sparse_layer.sample_bbox, dl, cost_out,
-                        self.batch_size, self.s0, self.s1, float(self.cost_factor), float(self.bbox_factor),
-                        bool(self.use_bounded_iou), fit_target=t.get("fit"), nfit=self.s2,
-                        fit_factor=float(self.indfit_factor))
+        if self.focal_gamma > 0.0:
+            ops.detect_loss_focal(lg, t["det"], t["valid"], t["reg"], self.sparse_layer.sample_bbox, dl, cost_out,
+                                  self.batch_size, self.s0, self.s1, float(self.cost_factor), float(self.bbox_factor),
+                                  self.focal_gamma, bool(self.use_bounded_iou), fit_target=t.get("fit"), nfit=self.s2,
+                                  fit_factor=float(self.indfit_factor))
+        else:
+            ops.detect_loss(lg, t["det"], t["valid"], t["reg"], self.sparse_layer.sample_bbox, dl, cost_out,
+                            self.batch_size, self.s0, self.s1, float(self.cost_factor), float(self.bbox_factor),
+                            bool(self.use_bounded_iou), fit_target=t.get("fit"), nfit=self.s2,
+                            fit_factor=float(self.indfit_factor))
         if want_grad:
             self.conv.output.grad = dl.view(logits.shape)
 

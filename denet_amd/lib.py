@@ -176,6 +176,7 @@ SIGNATURES = {
     "denet_corner_fwd": (I, [P, P] + [I] * 5 + [P]),
     "denet_loss_workspace_bytes": (Z, []),
     "denet_corner_loss": (I, [P] * 5 + [I] * 5 + [F, P]),
+    "denet_corner_loss_focal": (I, [P] * 5 + [I] * 5 + [F, F, P]),
     "denet_sparse_fwd": (I, [P, P, P, P] + [I] * 10 + [P]),
     "denet_sparse_sort_workspace_bytes": (Z, [I] * 5),
     "denet_sparse_sort_is_single": (I, [I] * 5),
@@ -186,6 +187,7 @@ SIGNATURES = {
     "denet_sparse_bilinear_sort": (I, [P, P, Z] + [I] * 5 + [P]),
     "denet_sparse_bilinear_bwd": (I, [P, P, P, P, Z, P] + [I] * 10 + [P]),
     "denet_detect_loss": (I, [P] * 9 + [I] * 6 + [F, F, F, I, P]),
+    "denet_detect_loss_focal": (I, [P] * 9 + [I] * 6 + [F, F, F, I, F, P]),
     "denet_detect_decode": (I, [P] * 5 + [I] * 6 + [F, P]),
     "denet_detect_nms": (I, [P] * 5 + [I, I, I, F, F, P]),
     "denet_soft_nms_batch_host": (L, [P, P, P, P, I, I, I, F, F, P, P, P, P, L]),

@@ -193,6 +193,9 @@ def train(args, train_data, log=None, test_data=None):
     model = model_cnn.initialize(args, train_data.get_data_shape(), train_data.class_labels, train_data.get_class_num())
     skip_train = getattr(args, "skip_train", False)
     set_gradient_norm_args(model, args, log)
+    from ..layer import focal_log_lines
+    for line in focal_log_lines(model):      # cost layers with focalGamma > 0 (opt-in)
+        log(line)
     if not skip_train:
         model.build_train_func(args.solver, args.cost_factors)
     learn_rate = args.learn_rate

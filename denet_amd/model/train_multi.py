@@ -71,6 +71,10 @@ def train(args, train_data, dp, log=None):
     # F = 1: every rank takes the norm of the same all-reduced gradient with a bit-reproducible kernel, so all ranks clip alike
     # without communicating; F > 1: every local step (acc mode: the one update of train_end) clips its own gradient
     train_mod.set_gradient_norm_args(model, args, log if dp is None or dp.rank == 0 else None)
+    if dp is None or dp.rank == 0:
+        from ..layer import focal_log_lines
+        for line in focal_log_lines(model):  # cost layers with focalGamma > 0 (opt-in)
+            log(line)
     model.build_train_func(args.solver, args.cost_factors, use_acc_mode=use_acc_mode)
     if dp is not None:
         if factor == 1:

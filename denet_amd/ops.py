@@ -61,7 +61,8 @@ def kernel_symbol(kind, a, b, c):
              24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
              33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel",
              50: "grad_norm_partial_kernel", 51: "grad_norm_finish_kernel", 52: "solver_coef_kernel", 53: "adam_coef_kernel",
-             60: "sparse_bilinear_fwd_kernel", 61: "sparse_bilinear_bwd_kernel"}.get(kind)
+             60: "sparse_bilinear_fwd_kernel", 61: "sparse_bilinear_bwd_kernel",
+             70: "corner_focal_loss_kernel", 71: "detect_focal_loss_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
 
 
@@ -2324,6 +2325,17 @@ def corner_loss(corner_pr, target, dconv, cost_out, cost_factor):
                                  cn, cost_factor, stream_ptr()), "corner_loss")
 
 
+def corner_loss_focal(corner_pr, target, dconv, cost_out, cost_factor, gamma):
+    """corner_loss with every term t_k * l_k weighted by (1 - p_k)^gamma (opt-in; csrc/focal.hip); gamma is
+    0 or finite and >= 1. Only the corner channels of dconv are written"""
+    B, _, cn, H, W = corner_pr.shape
+    CP = dconv.shape[-1] if dconv is not None else 0
+    check(_L().denet_corner_loss_focal(ptr(corner_pr), ptr(target), ptr(dconv), ptr(cost_out), ptr(_loss_ws()), B, H, W, CP,
+                                       cn, cost_factor, float(gamma), stream_ptr()), "corner_loss_focal")
+    if PROFILE is not None:
+        PROFILE.add(0.0)                   # (the record of the corner_focal_loss_kernel launch)
+
+
 def sparse_fwd_buffers(M, gs, kp):
     """the two outputs of sparse_fwd for M RoIs, allocated ahead of the call (the training step makes them before it waits for the RoI
     proposal: nothing but the launch stands between the bbox array and the gather)"""
@@ -2441,6 +2453,19 @@ def detect_loss(logits, det_target, bbox_valid, bbox_target, roi_bbox, dlogits, 
                                  ptr(fit_target), ptr(dlogits), ptr(costs), ptr(_loss_ws()), M, batch, CP, ncls, nreg,
                                  int(nfit), cost_factor, bbox_factor, float(fit_factor), int(bounded_iou), stream_ptr()),
           "detect_loss")
+
+
+def detect_loss_focal(logits, det_target, bbox_valid, bbox_target, roi_bbox, dlogits, costs, batch, ncls, nreg,
+                      cost_factor, bbox_factor, gamma, bounded_iou=False, fit_target=None, nfit=0, fit_factor=0.0):
+    """detect_loss with the class cost weighted by (1 - p_c)^gamma (opt-in; csrc/focal.hip); everything else
+    of the cost is detect_loss's, bit for bit. gamma is 0 or finite and >= 1"""
+    M, CP = logits.shape
+    check(_L().denet_detect_loss_focal(ptr(logits), ptr(det_target), ptr(bbox_valid), ptr(bbox_target), ptr(roi_bbox),
+                                       ptr(fit_target), ptr(dlogits), ptr(costs), ptr(_loss_ws()), M, batch, CP, ncls, nreg,
+                                       int(nfit), cost_factor, bbox_factor, float(fit_factor), int(bounded_iou), float(gamma),
+                                       stream_ptr()), "detect_loss_focal")
+    if PROFILE is not None:
+        PROFILE.add(0.0)                   # (the record of the detect_focal_loss_kernel launch)
 
 
 def regression_loss(logits, offsets, cls, dlogits, costs, C):

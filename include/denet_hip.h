@@ -661,6 +661,13 @@ int denet_corner_fwd(const float* conv, float* corner_pr, int B, int H, int W, i
 size_t denet_loss_workspace_bytes(void);
 int denet_corner_loss(const float* corner_pr, const float* target, float* dconv, float* cost, void* workspace, int B,
                       int H, int W, int CP, int Cn, float cost_factor, hipStream_t stream);
+/* opt-in focal corner cost (layer key focalGamma, `DNC[feat, cost, dropout, gamma]`; csrc/focal.hip): extends the cost of
+ * denet/layer/denet_corner.py:126-134, the reference has no such mode - the definition is DESIGN.md section 17. Arguments of
+ * denet_corner_loss plus gamma: each term t_k * l_k is weighted by (1 - p_k)^gamma. Only the Cn corner channels of dconv are
+ * written. Refused before any device call: gamma other than 0 or a finite value >= 1, null pointers, bad shapes. workspace:
+ * denet_loss_workspace_bytes(). */
+int denet_corner_loss_focal(const float* corner_pr, const float* target, float* dconv, float* cost, void* workspace, int B,
+                            int H, int W, int CP, int Cn, float cost_factor, float gamma, hipStream_t stream);
 
 /* ---- sparse RoI feature sampling  (denet/layer/denet_sparse_op.py:42-85 k_sparse_sample<gs>, :171-212
  *      k_sparse_sample_grad<gs>; Theano fallback denet/layer/denet_sparse.py:70-96)
@@ -715,6 +722,16 @@ int denet_detect_loss(const float* logits, const float* det_target, const float*
                       const float* roi_bbox, const float* fit_target, float* dlogits, float* costs, void* workspace, int M,
                       int batch, int CP, int ncls, int nreg, int nfit, float cost_factor, float bbox_factor,
                       float fit_factor, int bounded_iou, hipStream_t stream);
+/* opt-in focal detection cost (layer key focalGamma, `DND[overlap, cost, bbox, fit, gamma]`; csrc/focal.hip): extends the class
+ * cost of denet/layer/denet_detect.py:238-313 (get_errors :257), the reference has no such mode - the definition is DESIGN.md
+ * section 17. Arguments of denet_detect_loss plus gamma: class term t_c * lp_c is weighted by (1 - p_c)^gamma; the box
+ * regression, the independent-fitness cost, costs[1] and the zeroed padding columns are denet_detect_loss's, bit for bit.
+ * Refused before any device call: gamma other than 0 or a finite value >= 1, and what denet_detect_loss refuses. workspace:
+ * denet_loss_workspace_bytes(). */
+int denet_detect_loss_focal(const float* logits, const float* det_target, const float* bbox_valid, const float* bbox_target,
+                            const float* roi_bbox, const float* fit_target, float* dlogits, float* costs, void* workspace,
+                            int M, int batch, int CP, int ncls, int nreg, int nfit, float cost_factor, float bbox_factor,
+                            float fit_factor, int bounded_iou, float gamma, hipStream_t stream);
 
 /* ---- inference tail  (denet/layer/denet_detect.py:76-100 class log-softmax + box decoding, :330-349
  *      joint-fitness marginalisation; denet/layer/denet_detect.cc:99-173 build_detections_nms, :73-97 hard NMS,
