@@ -173,6 +173,8 @@ SIGNATURES = {
     "denet_grad_norm": (I, [P, P, I, I, F, F, P, P, P, P, P]),
     "denet_solver_step_coef": (I, [P, P, P, L, L, F, F, I, F, F, I, P, P]),
     "denet_solver_adam_coef": (I, [P, P, P, P, L, L, F, F, F, I, F, F, P, P]),
+    "denet_ema_update": (I, [P, P, L, F, P]),
+    "denet_swap": (I, [P, P, L, P]),
     "denet_corner_fwd": (I, [P, P] + [I] * 5 + [P]),
     "denet_loss_workspace_bytes": (Z, []),
     "denet_corner_loss": (I, [P] * 5 + [I] * 5 + [F, P]),

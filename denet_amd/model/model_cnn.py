@@ -24,6 +24,13 @@ from ..layer import Act, InitialLayer, round_up
 from ..layer.layer_types import layer_types
 
 SOLVER_MODES = {"sgd": 0, "torch": 1, "nesterov": 1, "adam": 2}
+EMA_WARMUP = (1, 10)      # the average's decay is min(d, (1 + t) / (10 + t)): DESIGN.md section 18
+
+
+def ema_decay_at(t, d):
+    """the decay of the average's update number t (t = 0 for the first) under the user's decay d: the usual warm-up, so that the
+    weights of the first steps are not frozen into the average. In double; ModelCNN.ema_step rounds 1 - decay to float32 once"""
+    return min(float(d), (EMA_WARMUP[0] + t) / (EMA_WARMUP[1] + t))
 
 
 def load_from_json(json_obj, batch_size=32, layer_range=None):
@@ -107,6 +114,38 @@ class StepContext:
         self.bn_probe = None       # (batch norm layer, acc, workspace): test mode accumulates the moments of its input (update_bn.py)
 
 
+class _EmaWeights:
+    """ModelCNN.ema_weights(): the parameters and statistics exchanged with their averages for the length of a block"""
+
+    def __init__(self, model):
+        self.model = model
+
+    def _exchange(self):
+        import torch
+        from .. import ops
+        m = self.model
+        torch.cuda.synchronize()         # every stream that reads or writes P / S is done
+        ops.swap(m.P, m.E)
+        ops.swap(m.S, m.ES)
+        torch.cuda.synchronize()
+        ops.bump_weights_version()       # Winograd filter caches and folded batch norms are rebuilt from what P holds now
+
+    def __enter__(self):
+        m = self.model
+        if m._ema_swapped:
+            raise RuntimeError("ema_weights() inside ema_weights(): the average is already in place")
+        if m.E is None or m.ema_updates == 0:
+            raise RuntimeError("ema_weights() before the first update of the average (ema_decay = %r, %i updates)" % (m.ema_decay, m.ema_updates))
+        self._exchange()
+        m._ema_swapped = True
+        return m
+
+    def __exit__(self, *exc):
+        self._exchange()
+        self.model._ema_swapped = False
+        return False
+
+
 class ModelCNN:
     def __init__(self):
         self.batch_size = 0
@@ -118,6 +157,11 @@ class ModelCNN:
         layer_mod.set_rng_seed(self.rng_seed)
         self.gradient_clip = 0.0   # > 0: every update is clipped to this global L2 norm; a training argument
         self.track_grad_norm = False   # the norm pass without a limit: last_grad_norm / grad_norm_stats / param_norms
+        self.ema_decay = 0.0       # in (0, 1): an average of P and S is kept on the device; a training argument
+        self.ema_auto = True       # False: the steps leave the update to the caller's ema_step() (train_multi behind average_state)
+        self.ema_updates = 0       # updates of the average so far (t of ema_decay_at)
+        self.E = self.ES = None    # the averages of P and S, allocated by the first training step with the mode on
+        self._ema_swapped = False  # inside ema_weights()
         self.skip_layer_updates = []
         self.bias_decay = False
         self.layers = []
@@ -296,6 +340,9 @@ class ModelCNN:
             self._weight_norm = torch.zeros(self._norm.n_segments, device="cuda")
             self._weight_norm_out = torch.zeros(2, device="cuda")
         self._norm_ran = False
+        self.E = self.ES = None    # new buffers: a new average
+        self.ema_updates = 0
+        self._ema_swapped = False
         ops.bump_weights_version()
 
     def build_train_func(self, solver_mode="sgd", cost_factors=[], use_acc_mode=False, skip_build=False):
@@ -327,6 +374,9 @@ class ModelCNN:
         clip = float(self.gradient_clip)
         if not math.isfinite(clip) or clip < 0.0:
             raise ValueError("gradient_clip = %r: the limit of the global gradient norm is 0 (off) or a positive finite number" % (self.gradient_clip,))
+        ema = float(self.ema_decay)
+        if not (ema == 0.0 or (math.isfinite(ema) and 0.0 < ema < 1.0)):
+            raise ValueError("ema_decay = %r: the decay of the weight average is 0 (off) or a finite number strictly between 0 and 1" % (self.ema_decay,))
         self.use_split_mode = False   # split points are identities here (288 GB of HBM)
         # `BN A` pairs whose batch-norm output nobody else reads run as the fused BN + ReLU (ActivationLayer; DENET_BN_ACT_FUSE=0: apart)
         for l in walk_layers(self.layers):
@@ -494,6 +544,7 @@ class ModelCNN:
     def train_begin(self):
         import torch
         assert self.use_acc_mode, "build_train_func(use_acc_mode=True) first"
+        self._ema_refuse("train_begin")
         if not self._packed:
             self.pack_device()
         self._acc = {"G": torch.zeros_like(self.G), "S": torch.zeros_like(self.S), "S0": self.S.clone(), "n": 0, "args": None}
@@ -512,6 +563,51 @@ class ModelCNN:
         ops.check(ops._L().denet_scale(self.S.data_ptr(), self.S.numel(), scale, ops.stream_ptr()), "scale")
         ops.bump_weights_version()
         self._acc = None
+        if self.ema_decay > 0.0 and self.ema_auto:
+            self.ema_step()                  # one update of the average per train_end, none per sub-step
+
+    # ---- an exponential moving average of the weights (csrc/ema.hip). No reference counterpart. With
+    # ema_decay = d in (0, 1), once per parameter update, right behind the solver on the compute stream:
+    #     e <- fmaf(om_t, p - e, e) over all of P into E and all of S into ES,   om_t = float32(1 - min(d, (1 + t) / (10 + t)))
+    # E / ES start as copies of P / S as they stand when the first training step with the mode on begins. The average only
+    # observes: nothing the step computes reads it. It is not saved with the model and not resumed.
+    def _ema_refuse(self, what):
+        if self._ema_swapped:
+            raise RuntimeError("%s inside ema_weights(): the parameter buffer holds the average, not the weights" % what)
+
+    def _ema_begin_step(self):
+        """at the start of every training step: refuses a step inside ema_weights(); with the mode on, the first one copies P and S"""
+        self._ema_refuse("train_step")
+        if self.ema_decay > 0.0 and self.E is None:
+            if not self._packed:
+                self.pack_device()
+            self.E, self.ES = self.P.clone(), self.S.clone()
+            self.ema_updates = 0
+
+    def ema_step(self):
+        """one update of the average: two launches on the current stream (P into E, S into ES), no host synchronisation. The steps
+        call it themselves while ema_auto holds (behind the solver; in acc mode behind train_end's one update)"""
+        from .. import ops
+        if not (0.0 < float(self.ema_decay) < 1.0):
+            raise RuntimeError("ema_step: ema_decay = %r, the average is off" % (self.ema_decay,))
+        self._ema_refuse("ema_step")
+        self._ema_begin_step()
+        om = float(numpy.float32(1.0 - ema_decay_at(self.ema_updates, self.ema_decay)))     # in double, rounded once
+        ops.ema_update(self.E, self.P, om)
+        ops.ema_update(self.ES, self.S, om)
+        self.ema_updates += 1
+
+    def ema_weights(self):
+        """context manager: inside the block the model IS its average. P <-> E and S <-> ES are exchanged in place, so every
+        Param.dev view stays valid and predictions, get_value() and save_to_file see the average; exchanged back on the way out, also
+        when the body raises. The device is synchronised around both exchanges (the filter-gradient stream and the side streams
+        read P and S): for epoch ends, never for the step loop. No training step, no nesting, and not before the first update"""
+        return _EmaWeights(self)
+
+    def save_ema(self, fname, compresslevel=9):
+        """the average as an ordinary model file (model-predict, model-modify and model-update-bn take it unchanged)"""
+        with self.ema_weights():
+            save_to_file(self, fname, compresslevel)
 
     # ---- global-norm gradient clipping and gradient norms (csrc/grad_norm.hip, DESIGN.md section 15). The reference's switch
     # (model_cnn.py:237-239) clips the gradient arriving at the cost, i.e. scales by min(1, c), and is never set; here
@@ -590,6 +686,7 @@ class ModelCNN:
         acc = self._acc if getattr(self, "use_acc_mode", False) else None
         if getattr(self, "use_acc_mode", False) and acc is None:
             raise Exception("--use-acc-mode: call train_begin() before train_step()")
+        self._ema_begin_step()
         if acc is not None:
             self.S.copy_(acc["S0"])            # every sub-step starts from the statistics at train_begin
         ctx = self.forward(data_x, data_m, train=True)
@@ -622,6 +719,8 @@ class ModelCNN:
             ops.solver_step(self.P[:self.n_trainable], self.M[:self.n_trainable], self.G[:self.n_trainable], n_decay,
                             float(learn_rate), float(momentum[0]), it, float(decay), SOLVER_MODES[self.solver_mode],
                             scale, coef=coef)
+        if acc is None and self.ema_decay > 0.0 and self.ema_auto:
+            self.ema_step()              # right behind the solver (sgd, nesterov and adam alike); acc mode: train_end
         ops.bump_weights_version()       # parameters and BN running statistics moved: inference caches are stale
         import torch
         if getattr(self, "input_consumed", None) is None:

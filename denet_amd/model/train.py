@@ -137,6 +137,11 @@ def build_parser(single=True):
     parser.add_argument("--gradient-norms", default=False, action="store_true",
                         help="opt-in: track the global gradient norm of every update on the device and log it at every epoch's end, "
                              "without clipping (at verbose level: the per-array gradient and weight norms too)")
+    parser.add_argument("--ema", type=float, default=0.0, metavar="DECAY",
+                        help="opt-in: keep an exponential moving average of the weights and the batch-norm statistics on the device "
+                             "(0 = off, else strictly between 0 and 1; the decay of update t is min(DECAY, (1 + t) / (10 + t)), DESIGN.md "
+                             "section 18). Every model file gets a sibling <prefix>_ema_epochNNN[...].mdl.gz, every test an `ema test "
+                             "error` line. The average is not saved with the model and not resumed (csrc/ema.hip)")
     parser.add_argument("--model-desc", default=["C[100,7]", "P[2]", "C[150,4]", "P[2]", "C[250,4]", "P[2]", "C[300,1]", "R"],
                         nargs="+", type=str)
     return parser
@@ -187,12 +192,37 @@ def gradient_norm_lines(model, args):
     return model.grad_norm_log_lines(verbose=bool(getattr(args, "gradient_norms", False)) and logging.verbose_enabled())
 
 
+def set_ema_args(model, args, log=None):
+    """--ema DECAY -> model.ema_decay (a training argument like the learning rate: not saved into the .mdl.gz); build_train_func
+    refuses anything but 0 or a finite value strictly between 0 and 1"""
+    model.ema_decay = float(getattr(args, "ema", 0.0) or 0.0)
+    if log is not None and model.ema_decay != 0.0:
+        log("an average of the weights is kept on the device (--ema %g): decay of update t = min(%g, (1 + t) / (10 + t)), written to "
+            "<prefix>_ema_epochNNN[...].mdl.gz beside every model file" % (model.ema_decay, model.ema_decay))
+        if getattr(args, "model", None) is not None:
+            log("the average is not resumed: it starts anew, warm-up included, from the weights of %s" % args.model)
+
+
+def ema_name(fname):
+    """the average's sibling of a checkpoint: `_ema` in front of `_epoch`, which train_multi.find_restart's glob does not match"""
+    head, sep, tail = fname.rpartition("_epoch")
+    assert sep, fname
+    return head + "_ema_epoch" + tail
+
+
+def save_ema_beside(model, fname):
+    """the average's model file beside the checkpoint `fname` (nothing while the mode is off or no update has run)"""
+    if model.ema_decay > 0.0 and model.ema_updates > 0:
+        model.save_ema(ema_name(fname))
+
+
 def train(args, train_data, log=None, test_data=None):
     """the epoch loop of train.py:117-151 (shuffle, train_epoch, learning-rate annealing, checkpoint per epoch)"""
     log = _default_log() if log is None else log
     model = model_cnn.initialize(args, train_data.get_data_shape(), train_data.class_labels, train_data.get_class_num())
     skip_train = getattr(args, "skip_train", False)
     set_gradient_norm_args(model, args, log)
+    set_ema_args(model, args, log)
     from ..layer import focal_log_lines
     for line in focal_log_lines(model):      # cost layers with focalGamma > 0 (opt-in, DESIGN.md section 17)
         log(line)
@@ -231,11 +261,18 @@ def train(args, train_data, log=None, test_data=None):
             test_error, test_class_errors = compute_error(test_data, model)
             log("epoch %i test error: %.2f%%" % (epoch, test_error))
             save_results(args.output_prefix + "_epoch%03i.test" % epoch, test_error, test_class_errors)
+            if model.ema_decay > 0.0 and model.ema_updates > 0:
+                with model.ema_weights():
+                    test_error, test_class_errors = compute_error(test_data, model)
+                log("epoch %i ema test error: %.2f%%" % (epoch, test_error))
+                save_results(ema_name(args.output_prefix + "_epoch%03i.test" % epoch), test_error, test_class_errors)
         if not args.disable_intermediate:
             model_cnn.save_to_file(model, args.output_prefix + "_epoch%03i.mdl.gz" % epoch)
+            save_ema_beside(model, args.output_prefix + "_epoch%03i.mdl.gz" % epoch)
     if device_loader is not None:
         device_loader.close()
     model_cnn.save_to_file(model, args.output_prefix + "_epoch%03i_final.mdl.gz" % (args.epochs - 1))
+    save_ema_beside(model, args.output_prefix + "_epoch%03i_final.mdl.gz" % (args.epochs - 1))
     return model, costs
 
 

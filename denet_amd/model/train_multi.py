@@ -22,7 +22,9 @@ Rank 0 writes the checkpoints with the reference's names: `<prefix>_epochNNN_fin
 `--epoch-start E` skips the first E epochs (the learning rate is annealed for them, train_multi.py:406-410; the shuffle seed is
 seed + epoch, so the data order of the remaining epochs is unchanged); `--restart` finds the newest `<prefix>_epoch*.mdl.gz`
 like load_restart_args (train_multi.py:242-268) and continues behind it. The momentum buffer is not part of a .mdl.gz (as in
-the reference): a restarted run begins with zero momentum."""
+the reference): a restarted run begins with zero momentum. `--ema DECAY` keeps an average of the weights on every rank (DESIGN.md
+section 18; rank 0 writes `<prefix>_ema_epochNNN[...].mdl.gz` beside every checkpoint, which the `--restart` glob does not match);
+with F > 1 the average is updated behind `average_state`, not inside the local steps. It is not resumed either."""
 import math
 import os
 import random
@@ -71,6 +73,10 @@ def train(args, train_data, dp, log=None):
     # F = 1: every rank takes the norm of the same all-reduced gradient with a bit-reproducible kernel, so all ranks clip alike
     # without communicating; F > 1: every local step (acc mode: the one update of train_end) clips its own gradient
     train_mod.set_gradient_norm_args(model, args, log if dp is None or dp.rank == 0 else None)
+    # the weight average (--ema): every rank keeps its own from bit-identical inputs, nothing is communicated.
+    # F > 1 over several ranks: the update runs behind dp.average_state, on the averaged state, not inside the local steps
+    train_mod.set_ema_args(model, args, log if dp is None or dp.rank == 0 else None)
+    model.ema_auto = not (dp is not None and factor > 1)
     if dp is None or dp.rank == 0:
         from ..layer import focal_log_lines
         for line in focal_log_lines(model):  # cost layers with focalGamma > 0 (opt-in)
@@ -127,11 +133,14 @@ def train(args, train_data, dp, log=None):
                     model.train_end()                                    # worker.py:114-116
                 if factor > 1 and dp is not None and (step + 1) % factor == 0:
                     dp.average_state(model)
+                    if model.ema_decay > 0.0:
+                        model.ema_step()                                 # ema_auto is off: one update per averaged state
             costs.append(cost)
             if rank == 0:
                 log("epoch %i subset %i - cost (rank 0): %.4f (lr %g, %i GPUs)" % (epoch, subset, cost, learn_rate, world))
                 if getattr(args, "save_subsets", False) and not args.disable_intermediate:
                     model_cnn.save_to_file(model, args.output_prefix + "_epoch%03i_subset%03i.mdl.gz" % (epoch, subset + 1))
+                    train_mod.save_ema_beside(model, args.output_prefix + "_epoch%03i_subset%03i.mdl.gz" % (epoch, subset + 1))
         if rank == 0:
             for line in train_mod.gradient_norm_lines(model, args):
                 log("epoch %i %s (rank 0)" % (epoch, line))
@@ -139,6 +148,7 @@ def train(args, train_data, dp, log=None):
             learn_rate *= args.learn_anneal
         if rank == 0 and (not args.disable_intermediate or epoch == args.epochs - 1):
             model_cnn.save_to_file(model, args.output_prefix + "_epoch%03i_final.mdl.gz" % epoch)     # train_multi.py:166
+            train_mod.save_ema_beside(model, args.output_prefix + "_epoch%03i_final.mdl.gz" % epoch)
     if loader is not None:
         loader.close()
     return model, costs

@@ -61,6 +61,7 @@ def kernel_symbol(kind, a, b, c):
              24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
              33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel",
              50: "grad_norm_partial_kernel", 51: "grad_norm_finish_kernel", 52: "solver_coef_kernel", 53: "adam_coef_kernel",
+             54: "ema_update_kernel", 55: "swap_kernel",
              60: "sparse_bilinear_fwd_kernel", 61: "sparse_bilinear_bwd_kernel",
              70: "corner_focal_loss_kernel", 71: "detect_focal_loss_kernel"}.get(kind)
     return fixed or "igemm_kernel<%d, %d, %d, 2, 2, %d>" % (kind, a, b, c)
@@ -2305,6 +2306,29 @@ def grad_norm(x, nt, scale=1.0, clip=0.0, seg_norm=None, out=None, stats=None):
     check(_L().denet_grad_norm(ptr(x), ptr(nt.table), nt.n_chunks, nt.n_segments, float(scale), float(clip), ptr(nt.workspace),
                                ptr(seg_norm), ptr(out), ptr(stats), stream_ptr()), "grad_norm")
     return out
+
+
+# ---- exponential moving average of the weights (csrc/ema.hip): opt-in, no reference counterpart
+EMA_KERNELS = ("ema_update_kernel", "swap_kernel")      # what the average adds: one update per buffer behind the solver; the exchange
+
+
+def _flat_pair(a, b, what):
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_cuda and b.is_cuda, what + ": float32 device tensors"
+    assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel() and a.numel() >= 1, (what, a.numel(), b.numel())
+
+
+def ema_update(e, p, om):
+    """one launch on the current stream: e <- fmaf(om, p - e, e) elementwise, the subtraction rounded on its own. om = 1 - decay,
+    rounded to float32 once by the caller. Any length and any alignment of the two tensors"""
+    _flat_pair(e, p, "ema_update")
+    check(_L().denet_ema_update(ptr(e), ptr(p), e.numel(), float(om), stream_ptr()), "ema_update")
+    return e
+
+
+def swap(a, b):
+    """one launch on the current stream: the contents of a and b exchanged in place, bit for bit"""
+    _flat_pair(a, b, "swap")
+    check(_L().denet_swap(ptr(a), ptr(b), a.numel(), stream_ptr()), "swap")
 
 
 def corner_fwd(conv, cn):

@@ -654,6 +654,18 @@ int denet_solver_adam_coef(float* params, float* m, float* v, const float* grads
                            float beta1, float beta2, int iteration, float decay, float grad_scale, const float* coef,
                            hipStream_t stream);
 
+/* ---- OPT-IN exponential moving average of the weights (csrc/ema.hip; ModelCNN.ema_decay, model-train --ema DECAY). No reference
+ *      counterpart: the reference keeps no average of its weights, the definition is this build's. The
+ *      default step makes neither call.
+ *   ema_update    e[i] <- fmaf(om, p[i] - e[i], e[i]) for i in [0, n): the subtraction rounded on its own, om = float32(1 - decay)
+ *                 formed by the caller, inside [0, 1]. Where p[i] == e[i] the entry keeps its value. No reference counterpart.
+ *   swap          a[i] <-> b[i] for i in [0, n), exact (ModelCNN.ema_weights exchanges the parameters and their average in
+ *                 place). No reference counterpart.
+ *   Both: any n >= 1 and any 4-byte aligned pointers (16-byte vectors on the aligned body, scalars in front and behind; all
+ *   scalars when the two pointers sit differently inside their 16 bytes); the ranges must not overlap. No atomics.           */
+int denet_ema_update(float* e, const float* p, long n, float om, hipStream_t stream);
+int denet_swap(float* a, float* b, long n, hipStream_t stream);
+
 /* ---- DeNet corner map  (denet/layer/denet_corner.py:50-53 log_softmax([x,-x]); :126-134 cost)
  *      conv:[B,H,W,CP] (first Cn channels are corner logits)  corner_pr/target:[B,2,Cn,H,W] (the reference's
  *      own layout, it is what build_samples consumes).  cost[0] receives cost_factor*corner_cost.         */
