@@ -3,6 +3,7 @@
 The library is built IN-TREE (denet_amd/csrc/libdenet_hip.so) so that it travels with the repository
 snapshot to the GPU box; hipcc cross-compiles gfx950 code objects without a GPU present.
 """
+import glob
 import hashlib
 import os
 import subprocess
@@ -58,8 +59,8 @@ def build(force=False, verbose=False):
         hipcc = "hipcc"
     version = _hipcc_version(hipcc)
     objs, todo = [], []
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "bn_final.h"), os.path.join(CSRC, "bf16_mma.h"),
-               os.path.join(HERE, "..", "include", "denet_hip.h")]
+    # every header there is: one added later cannot be left out of the digests
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "denet_hip.h")])
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, src.replace(".hip", ".o"))

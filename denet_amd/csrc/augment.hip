@@ -11,6 +11,7 @@
 // between forward and backward (the backward pass regenerates the same bits from the same counter).
 // The CPU checker under tests/ restates the generator bit for bit.
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

@@ -8,6 +8,7 @@
 // Per-channel reductions are accumulated in fp64 per thread, combined through LDS, written as
 // per-workgroup partials and finished by a second tiny kernel: deterministic, no atomics.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <stdlib.h>
 
 namespace {
@@ -681,11 +682,6 @@ extern "C" int denet_bn_bwd(const float* x, const float* y, const float* dy, con
 // denet_bn_workspace_bytes(M, C)) or denet_bn_fwd_train_pre (partial / rows from the convolution in front; workspace optional:
 // with it a list of more than 2048 rows is folded in two stages); the pooled
 // output y_pool [N,OH,OW,C] and its argmax taps are written, relu(bn(x)) itself is not (batch_norm_relu.py:34-48 + pool.py:38)
-extern "C" int denet_bn_relu_pool_fwd_train_xhat(const float* x, float* y_pool, unsigned char* argmax, float* xhat_pool,
-                                                 const float* gamma, const float* beta, float* run_mean, float* run_stdinv,
-                                                 float* save_mean, float* save_invstd, const double* partial, int rows,
-                                                 void* workspace, int N, int H, int W, int C, int OH, int OW, int k, int stride,
-                                                 int pad, float momentum, float eps, hipStream_t stream);
 extern "C" int denet_bn_relu_pool_fwd_train(const float* x, float* y_pool, unsigned char* argmax, const float* gamma,
                                             const float* beta, float* run_mean, float* run_stdinv, float* save_mean,
                                             float* save_invstd, const double* partial, int rows, void* workspace, int N, int H,

@@ -12,6 +12,7 @@
 // finish: acc, n -> run_mean = f32(acc0 / n), run_stdinv = 1 / sqrt(f32(acc1 / n) + 1e-5) in float32 with correctly rounded
 // add, square root and division (update_bn.py:63-66 evaluated by numpy in float32).
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

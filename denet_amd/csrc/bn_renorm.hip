@@ -27,18 +27,8 @@
 //                                  gradient slab; the slab never holds s2
 // state [4][C] floats: r | d | gamma_eff | beta_eff, written by the forward call, read by the backward call of the same step.
 #include "bn_final.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
-
-extern "C" size_t denet_bn_workspace_bytes(long M, int C);
-extern "C" int denet_bn_stats_partial(const float* x, void* workspace, int* rows, long M, int C, hipStream_t stream);
-extern "C" int denet_bn_apply(const float* x, const float* res, float* y, const float* gamma, const float* beta,
-                              const float* save_mean, const float* save_invstd, long M, int C, int relu, hipStream_t stream);
-extern "C" int denet_bn_bwd_sums(const float* x, const float* y, const float* dy, const float* gamma, const float* beta,
-                                 const float* save_mean, const float* save_invstd, float* dgamma, float* dbeta, float* coef,
-                                 void* workspace, long M, int C, int relu, hipStream_t stream);
-extern "C" int denet_bn_bwd_apply(const float* x, const float* y, const float* dy, const float* gamma, const float* beta,
-                                  const float* save_mean, const float* save_invstd, const float* coef, float* dx, float* dres,
-                                  long M, int C, int relu, hipStream_t stream);
 
 namespace {
 

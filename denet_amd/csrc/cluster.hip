@@ -28,6 +28,7 @@
 //                          its component, compaction in rank order (wave ballots + prefix over the wave counts), cut, outputs
 // Compiled with -ffp-contract=off.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
 
 namespace {

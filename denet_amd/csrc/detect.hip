@@ -8,6 +8,7 @@
 //                            scores, sequential by construction) — host code on the candidates kept by the GPU
 // Compiled with -ffp-contract=off: IoU comparisons against a threshold must not depend on FMA contraction.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
 #include <string.h>
 #include <vector>

@@ -7,6 +7,7 @@
 //                                                    denet/common/theano_util.py:27-34
 // This file is compiled with -ffp-contract=off: tap indices must be reproducible bit for bit.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <stdlib.h>
 #include <math.h>
 

@@ -4,6 +4,7 @@
 //   the plain `A` relu layer (denet/layer/activation.py:31-34), conv-bias gradient (column sums),
 //   and the fused solver update (denet/model/model_cnn.py:282-294, 321-331).
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
 
 namespace {

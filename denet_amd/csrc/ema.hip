@@ -12,6 +12,7 @@
 //   swap_kernel        a[i] <-> b[i] with the same split; exact (bits are moved, nothing is computed).
 // No atomics; plain vector stores. One pass moves 3 x 4 x n bytes (update: two reads, one write) or 4 x 4 x n (swap).
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 #define EMA_MAX_BLOCKS 2048   // 256 CUs x 8 workgroups of 256 threads: one resident set, the rest by the grid stride
 

@@ -6,6 +6,7 @@
 // This file is compiled with -ffp-contract=off like dss.hip: the box regression and independent-fitness terms are the plain
 // kernel's statements and must give its bits.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
 
 namespace {

@@ -12,6 +12,7 @@
 // this one is multiplied), split, and written to LDS as four bf16 images (A_hi, A_lo, B_hi, B_lo; rows padded to 80 bytes:
 // the 16-byte fragment reads of 16 consecutive rows cover all 64 banks).
 #include "bf16_mma.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

@@ -27,6 +27,7 @@
 // multiplied by *coef in a multiply of its own that the compiler may not contract into the decay FMA: coef = 1 leaves every bit
 // of the plain step.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
 
 #define DENET_GRAD_NORM_CHUNK 8192          // floats per chunk: a compile-time constant, the same on every device and grid

@@ -1111,19 +1111,6 @@ extern "C" int denet_conv_profile_read(int i, float* ms, int* mode, int* bm, int
     return DENET_OK;
 }
 
-extern "C" int denet_conv_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int N,
-                              int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
-                              int OW, hipStream_t stream);
-extern "C" int denet_conv_fwd_act(const float* x, const float* w, const float* bias, const float* add, float* y, int relu,
-                                  int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
-                                  int OW, hipStream_t stream);
-extern "C" int denet_conv_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W,
-                                int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW,
-                                hipStream_t stream);
-extern "C" int denet_conv_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes,
-                                int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad,
-                                int OH, int OW, hipStream_t stream);
-
 // Batch of `batch` independent GEMMs out_b[M,Nc] = a_b[M,Kc] * w_b[Nc,Kc]^T (all row-major, K contiguous): the component
 // products of the Winograd path (winograd.hip). Strides in elements. A measured choice (denet_gemm_batched_tune) is
 // TuneVal{tile, nbuf, 0}: tile 0 = 128 x 128, 1 = 128 x 64; nbuf = loop structure. (Round 2's persistent stream-K kernel for

@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

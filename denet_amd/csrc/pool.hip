@@ -4,6 +4,7 @@
 //        denet/layer/pool_inv_op.py:38-63 (k_pool_inv), :144-169 (k_pool_inv_grad)
 // All HBM-bound; one thread per float4 of channels per output pixel, grid-stride.
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

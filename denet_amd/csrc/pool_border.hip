@@ -9,6 +9,7 @@
 //     average : every tap of a window receives dy / count(window).
 // The window is given per axis. All HBM-bound; one thread per float4 of channels per pixel, grid-stride, as pool.hip.
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

@@ -13,6 +13,7 @@
 //        No atomics: the cost and the gradient are bitwise the same from run to run.
 // probs: one wave per sample: for v = 0 .. V-1 in order, softmax of the view added into pr[b][c]; then pr /= V.
 #include "common.h"
+#include "../../include/denet_hip.h"
 
 namespace {
 

@@ -2,6 +2,7 @@
 // PyErr_Format + %(fail)s (denet_sparse_op.py:137-142); here every entry point returns an int status and
 // leaves a thread-local message behind.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <stdarg.h>
@@ -351,8 +352,6 @@ extern "C" int denet_host_edit_samples_stream(const uint32_t* stream, long n_str
 // The host's whole share of the RoI hand-off in ONE call, for the moment the device stands idle between its proposal and the
 // gather: denet_samples_finish_host (sample tuples from the packed proposal: det_out [B][S][5]) followed by
 // denet_host_edit_samples_stream on them. Same outputs as the two calls.
-extern "C" int denet_samples_finish_host(const int* box_host, const float* absd_host, const int* count_host, int B,
-                                         int sample_count, int H, int W, float* samples_host);
 extern "C" int denet_host_handoff_stream(const uint32_t* stream, long n_stream, long* cursor, int* exhausted, const int* box_host,
                                          const float* absd_host, const int* count_host, int H, int W, int B, int S, int n_keep,
                                          const double* gt, const int* gt_off, int sample_gt, int* ws, float* det_out, double* out_pr,

@@ -21,6 +21,7 @@
 // denet_samples_finish_host with the same libm expression as the reference (denet_sparse.cc:306).
 // Compiled with -ffp-contract=off.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <math.h>
 #include <string.h>
 

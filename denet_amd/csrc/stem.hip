@@ -17,6 +17,7 @@
 //     through LDS, one partial per workgroup goes to the workspace and stem_wgrad_reduce_kernel adds the partials in workgroup
 //     order (bit-reproducible) into KRSC.
 #include "common.h"
+#include "../../include/denet_hip.h"
 #include <stdlib.h>
 
 namespace {
@@ -441,11 +442,6 @@ extern "C" int denet_conv_stem_ok(int pass, int N, int H, int W, int C, int K, i
            W % 2 == 0 && OH == H / 2 && OW == W / 2 && N > 0 && (long)N * H * W * 4 < (1L << 31);
 }
 
-extern "C" int denet_conv_stem_fwd_from(const float* x, int x_nchw, const float* w, const float* bias, float* y, double* stats_partial,
-                                        size_t stats_bytes, int* stats_rows, int N, int H, int W, hipStream_t stream);
-extern "C" int denet_conv_stem_wgrad_from(const float* x, int x_nchw, const float* dy, float* dw, float* workspace,
-                                          size_t workspace_bytes, int N, int H, int W, hipStream_t stream);
-
 // y = conv7x7/2(x) (+ bias) for x [N][H][W][4] (4th channel ignored), w [64][7][8][4]; stats_partial (optional): the batch-norm
 // column sums of y, [rows][2][64] doubles with rows = the launch's workgroups (<= 256 on this chip; *stats_rows receives it)
 extern "C" int denet_conv_stem_fwd(const float* x, const float* w, const float* bias, float* y, double* stats_partial,
@@ -455,9 +451,6 @@ extern "C" int denet_conv_stem_fwd(const float* x, const float* w, const float* 
 
 // the same; x_nchw != 0: x is the image batch as the reference holds it, [N][3][H][W] (dataset/__init__.py:359, the layout
 // model_cnn.py feeds the first layer) - no NHWC copy of the input has to exist
-extern "C" int denet_conv_stem_fwd_act(const float* x, int x_nchw, const float* w, const float* bias, float* y, int relu,
-                                       double* stats_partial, size_t stats_bytes, int* stats_rows, int N, int H, int W,
-                                       hipStream_t stream);
 extern "C" int denet_conv_stem_fwd_from(const float* x, int x_nchw, const float* w, const float* bias, float* y, double* stats_partial,
                                         size_t stats_bytes, int* stats_rows, int N, int H, int W, hipStream_t stream) {
     return denet_conv_stem_fwd_act(x, x_nchw, w, bias, y, 0, stats_partial, stats_bytes, stats_rows, N, H, W, stream);

@@ -670,10 +670,6 @@ extern "C" int denet_conv_wino2f_ok(int N, int H, int W, int Ci, int Co) {
 // (denet_conv_wino_filter with tile 2: dgrad = 0 for the forward pass, 1 for the data gradient, where x = dy, Co = C).
 // stats_partial (optional): [rows][2][Co] doubles, the batch-norm column sums of y (see denet_conv_fwd_stats); rows = the launch's
 // workgroups for Co = 64, N*ceil(H/16)*ceil(W/16) otherwise (the most the buffer must hold); *stats_rows receives rows.
-extern "C" int denet_conv_wino2f_sums(const float* x, const float* u, const float* bias, const float* add, float* y, int relu,
-                                      double* stats_partial, size_t stats_bytes, int* stats_rows, const denet_bn_link* sums_of,
-                                      int N, int H, int W, int Ci, int Co, hipStream_t stream);
-
 extern "C" int denet_conv_wino2f(const float* x, const float* u, const float* bias, const float* add, float* y, int relu,
                                  double* stats_partial, size_t stats_bytes, int* stats_rows, int N, int H, int W, int Ci,
                                  int Co, hipStream_t stream) {

@@ -1,13 +1,21 @@
-"""ctypes binding of libdenet_hip.so (include/denet_hip.h).
+"""ctypes binding of libdenet_hip.so, derived from include/denet_hip.h.
 
 This is the only door from the Python host side to the HIP kernels: plain pointers, sizes and a stream.
 There is deliberately NO fallback: if the library is missing or a call fails the caller gets an exception.
+The header is the only statement of the ABI: SIGNATURES, DEFINES and BnLink are parsed from it at import, nothing is typed twice.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libdenet_hip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "denet_hip.h")
+
+
+class DenetHipError(RuntimeError):
+    pass
+
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -17,198 +25,72 @@ Z = ctypes.c_size_t
 U64 = ctypes.c_uint64
 D = ctypes.c_double
 
-# name -> (restype, argtypes); mirrors include/denet_hip.h declaration by declaration
-SIGNATURES = {
-    "denet_last_error": (ctypes.c_char_p, []),
-    "denet_abi_version": (I, []),
-    "denet_device_info": (I, [I, P, P, P, I]),
-    "denet_host_py_random_sample": (I, [P, P, I, I, P, P]),
-    "denet_host_edit_samples": (I, [P, P, P, P, I, I, I, P, P, I, P, P, P, P]),
-    "denet_host_mt_prefetch": (I, [P, P, L, P, P, P, I, P]),
-    "denet_host_edit_samples_stream": (I, [P, L, P, P, P, P, I, I, I, P, P, I, P, P, P, P]),
-    "denet_host_handoff_stream": (I, [P, L, P, P, P, P, P, I, I, I, I, I, P, P, I, P, P, P, P, P]),
-    "denet_host_handoff_boxes_stream": (I, [P, L, P, P, P, P, I, I, I, I, I, P, P, I, P, P]),
-    "denet_host_handoff_boxes_stream_u": (I, [P, L, P, P, P, P, I, I, I, I, I, P, P, I, P, P, P]),
-    "denet_host_mt_uniforms": (I, [P, L, P]),
-    "denet_host_detect_targets": (I, [P, P, P, P, I, I, I, I, I, I, ctypes.c_double, ctypes.c_double, P, P, P, P]),
-    "denet_conv_fwd": (I, [P, P, P, P, P] + [I] * 12 + [P]),
-    "denet_conv_fwd_act": (I, [P, P, P, P, P] + [I] * 13 + [P]),
-    "denet_spin": (I, [I, P]),
-    "denet_tune_export": (I, [P, I]),
-    "denet_tune_import": (I, [P, I]),
-    "denet_tune_clear": (I, []),
-    "denet_conv_fwd_stats": (I, [P, P, P, P, P, P, Z, P] + [I] * 12 + [P]),
-    "denet_conv_dgrad": (I, [P, P, P, P] + [I] * 12 + [P]),
-    "denet_conv_rect_fwd": (I, [P] * 5 + [I] * 15 + [P]),
-    "denet_conv_rect_dgrad": (I, [P] * 4 + [I] * 14 + [P]),
-    "denet_conv_rect_wgrad_workspace_bytes": (Z, [I] * 7),
-    "denet_conv_rect_wgrad": (I, [P] * 4 + [Z] + [I] * 14 + [P]),
-    "denet_filter_to_bf16": (I, [P, P, L, P]),
-    "denet_conv_fwd_bf16": (I, [P] * 5 + [I] * 13 + [P]),
-    "denet_filter_to_bf16_dgrad": (I, [P, P, I, I, I, I, P]),
-    "denet_conv_dgrad_bf16": (I, [P] * 4 + [I] * 12 + [P]),
-    "denet_conv_wgrad_bf16_slices": (I, [I] * 7),
-    "denet_conv_wgrad_bf16_workspace_bytes": (Z, [I] * 7),
-    "denet_conv_wgrad_bf16": (I, [P] * 4 + [Z] + [I] * 12 + [P]),
-    "denet_conv_wgrad_workspace_bytes": (Z, [I] * 7),
-    "denet_conv_wino_workspace_bytes": (Z, [I] * 6),
-    "denet_conv_wino_tune": (I, [P, Z, P, Z] + [I] * 6 + [P]),
-    "denet_conv_wino_wgrad": (I, [P, P, P, P, P, Z, P, Z] + [I] * 6 + [P]),
-    "denet_conv_wino_filter": (I, [P, P, I, I, I, I, P]),
-    "denet_conv_wino_fwd": (I, [P] * 8 + [Z] + [I] * 6 + [P]),
-    "denet_conv_wino_fwd_act": (I, [P] * 7 + [I, P, Z] + [I] * 6 + [P]),
-    "denet_conv_wino_fwd_stats": (I, [P] * 8 + [Z, P, P, Z] + [I] * 6 + [P]),
-    "denet_conv_wino_fwd_stats_up": (I, [P] * 8 + [Z, P, P, Z] + [I] * 6 + [P]),
-    "denet_conv_wino_dgrad": (I, [P] * 6 + [Z] + [I] * 6 + [P]),
-    "denet_gemm_bf16x3_ok": (I, [I] * 3),
-    "denet_gemm_bf16x3_nt": (I, [P] * 4 + [I] * 3 + [P]),
-    "denet_transpose_f32": (I, [P, P, I, I, P]),
-    "denet_conv_wino2f_ok": (I, [I] * 5),
-    "denet_conv_wino2f": (I, [P] * 5 + [I, P, Z, P] + [I] * 5 + [P]),
-    "denet_conv_wino2f_wgrad_ok": (I, [I] * 5),
-    "denet_conv_wino2f_wgrad_workspace_bytes": (Z, [I] * 3),
-    "denet_conv_wino2f_wgrad": (I, [P] * 4 + [Z] + [I] * 5 + [P]),
-    "denet_conv_stem_ok": (I, [I] * 13),
-    "denet_conv_stem_fwd": (I, [P] * 5 + [Z, P] + [I] * 3 + [P]),
-    "denet_conv_stem_fwd_from": (I, [P, I] + [P] * 4 + [Z, P] + [I] * 3 + [P]),
-    "denet_conv_stem_wgrad_from": (I, [P, I] + [P] * 3 + [Z] + [I] * 3 + [P]),
-    "denet_conv_stem_fwd_act": (I, [P, I] + [P] * 3 + [I, P, Z, P] + [I] * 3 + [P]),
-    "denet_conv_stem_wgrad_workspace_bytes": (Z, []),
-    "denet_conv_stem_wgrad": (I, [P] * 4 + [Z] + [I] * 3 + [P]),
-    "denet_conv_tune": (I, [I, P, P, P, P, P, P, Z] + [I] * 12 + [P]),
-    "denet_conv_tuned": (I, [I] * 11 + [P, P, P]),
-    "denet_conv_last_config": (I, [P] * 5),
-    "denet_conv_wino4f_mode": (I, [I]),
-    "denet_conv_wino4g_mode": (I, [I]),
-    "denet_conv_profile": (I, [I]),
-    "denet_conv_profile_count": (I, []),
-    "denet_conv_profile_read": (I, [I] + [P] * 5),
-    "denet_conv_wgrad": (I, [P, P, P, P, Z] + [I] * 12 + [P]),
-    "denet_bn_final_arm_stats": (I, [L, I, F, F, P, P, P, P, P, I]),
-    "denet_bn_final_arm_sums": (I, [L, I, P, P, P, P, I]),
-    "denet_bn_final_disarm": (I, []),
-    "denet_bn_final_mode": (I, [I]),
-    "denet_bn_workspace_bytes": (Z, [L, I]),
-    "denet_bn_fwd_train": (I, [P] * 10 + [L, I, F, F, I, P]),
-    "denet_bn_fwd_train_pre": (I, [P] * 10 + [I, L, I, F, F, I, P]),
-    "denet_bn_relu_pool_fwd_train": (I, [P] * 10 + [I, P] + [I] * 9 + [F, F, P]),
-    "denet_bn_relu_pool_bwd": (I, [P] * 11 + [I] * 9 + [P]),
-    "denet_bn_relu_pool_fwd_train_xhat": (I, [P] * 11 + [I, P] + [I] * 9 + [F, F, P]),
-    "denet_bn_relu_pool_bwd_sums": (I, [P] * 9 + [I] * 6 + [P]),
-    "denet_bn_relu_pool_bwd_apply": (I, [P] * 9 + [I] * 9 + [P]),
-    "denet_bn_fold": (I, [P] * 6 + [F, P, P, I, L, P]),
-    "denet_bn_stats_final": (I, [P, I, L, I, F, F, P, P, P, P, P]),
-    "denet_bn_stats_partial": (I, [P, P, P, L, I, P]),
-    "denet_bn_renorm_workspace_bytes": (Z, [L, I]),
-    "denet_bn_renorm_fwd_train": (I, [P] * 11 + [I, P, L, I, F, F, F, F, I, P]),
-    "denet_bn_renorm_bwd": (I, [P] * 11 + [L, I, I, P]),
-    "denet_bn_apply": (I, [P] * 7 + [L, I, I, P]),
-    "denet_bn_bwd_sums": (I, [P] * 11 + [L, I, I, P]),
-    "denet_bn_bwd_apply": (I, [P] * 10 + [L, I, I, P]),
-    "denet_conv_wino_fwd_fold": (I, [P] * 7 + [I, P, Z, P, P, Z] + [I] * 6 + [P]),
-    "denet_conv_wino_dgrad_fold": (I, [P] * 8 + [Z, P, P, Z] + [I] * 6 + [P, P]),
-    "denet_conv_wino_dgrad_sums": (I, [P] * 7 + [Z, P, P, Z] + [I] * 6 + [P]),
-    "denet_conv_dgrad_sums": (I, [P] * 6 + [Z, P] + [I] * 12 + [P]),
-    "denet_conv_dgrad_1x1t": (I, [P] * 6 + [Z, P] + [I] * 5 + [P]),
-    "denet_conv_dgrad_t": (I, [P] * 6 + [Z, P] + [I] * 12 + [P]),
-    "denet_conv_wino2f_sums": (I, [P] * 5 + [I, P, Z, P, P] + [I] * 5 + [P]),
-    "denet_conv_dgrad_s2_ok": (I, [I] * 5),
-    "denet_conv_dgrad_s2_stats_rows": (I, [I] * 3),
-    "denet_conv_dgrad_s2_pack": (I, [P, P, I, I, P]),
-    "denet_conv_dgrad_s2": (I, [P] * 6 + [Z, P] + [I] * 5 + [P]),
-    "denet_conv_wino4t_ok": (I, [I] * 5),
-    "denet_conv_wino4t_stats_rows": (I, [I] * 3),
-    "denet_conv_wino4t_pack": (I, [P, P, I, I, P]),
-    "denet_conv_wino4t_sums": (I, [P] * 5 + [I, P, Z, P, P] + [I] * 5 + [P]),
-    "denet_bn_bwd_final": (I, [P, I, L, I, P, P, P, P]),
-    "denet_conv_wino_wgrad_dm": (I, [P, P, P, P, P, Z, P, Z] + [I] * 6 + [P]),
-    "denet_bn_fwd_test": (I, [P] * 8 + [I, L, I, F, I, P]),
-    "denet_bn_moments_workspace_bytes": (Z, [L, I]),
-    "denet_bn_moments_accumulate": (I, [P, P, P, Z, L, I, P]),
-    "denet_bn_moments_finish": (I, [P, L, F, P, P, I, P]),
-    "denet_regression_workspace_bytes": (Z, [I, I]),
-    "denet_regression_loss": (I, [P] * 6 + [Z] + [I] * 5 + [P]),
-    "denet_regression_probs": (I, [P] * 3 + [I] * 5 + [P]),
-    "denet_bn_bwd": (I, [P] * 12 + [L, I, I, P]),
-    "denet_maxpool_fwd": (I, [P, P, P] + [I] * 9 + [P]),
-    "denet_maxpool_bwd": (I, [P, P, P] + [I] * 9 + [P]),
-    "denet_avgpool_fwd": (I, [P, P] + [I] * 9 + [P]),
-    "denet_avgpool_bwd": (I, [P, P] + [I] * 9 + [P]),
-    "denet_pool_inv_fwd": (I, [P, P] + [I] * 6 + [P]),
-    "denet_pool_inv_bwd": (I, [P, P] + [I] * 6 + [P]),
-    "denet_maxpool_border_fwd": (I, [P, P] + [I] * 10 + [P]),
-    "denet_maxpool_border_bwd": (I, [P, P, P, P] + [I] * 10 + [P]),
-    "denet_avgpool_border_fwd": (I, [P, P] + [I] * 10 + [P]),
-    "denet_avgpool_border_bwd": (I, [P, P] + [I] * 10 + [P]),
-    "denet_host_resample_coeffs": (I, [I, D, D, I, I, P, P, L]),
-    "denet_image_crop": (I, [P, P] + [I] * 9 + [P]),
-    "denet_image_reduce": (I, [P, P, I, I, I, I, P]),
-    "denet_image_resample_pass": (I, [P, P, I, I, I, I, P, P, I, P]),
-    "denet_image_render_batch": (I, [I] + [P] * 13 + [I, I, P, P, Z, P, P, P, Z, P, P]),
-    "denet_image_finish": (I, [P, P, I, I, I, I, P, P, P, P, I, P, P]),
-    "denet_border_fwd": (I, [P, P] + [I] * 8 + [P]),
-    "denet_border_bwd": (I, [P, P] + [I] * 8 + [P]),
-    "denet_crop_mirror_fwd": (I, [P, P] + [I] * 6 + [F, F, I, U64, P]),
-    "denet_crop_mirror_bwd": (I, [P, P] + [I] * 6 + [F, F, I, U64, P]),
-    "denet_dropout": (I, [P, P, I, I, I, I, F, U64, P]),
-    "denet_concat_fwd": (I, [P, P, P, L] + [I] * 5 + [P]),
-    "denet_concat_bwd": (I, [P, P, P, L] + [I] * 5 + [P]),
-    "denet_add_bias": (I, [P, P, P, L, I, P]),
-    "denet_nchw_to_nhwc": (I, [P, P] + [I] * 5 + [P]),
-    "denet_nhwc_to_nchw": (I, [P, P] + [I] * 5 + [P]),
-    "denet_add": (I, [P, P, P, L, I, P]),
-    "denet_relu_fwd": (I, [P, P, L, P]),
-    "denet_relu_bwd": (I, [P, P, P, L, P]),
-    "denet_act_fwd": (I, [P, P, L, I, I, I, P]),
-    "denet_act_bwd": (I, [P, P, P, L, I, I, I, P]),
-    "denet_add_act_fwd": (I, [P, P, P, L, I, I, I, P]),
-    "denet_colsum_workspace_bytes": (Z, [L, I]),
-    "denet_colsum": (I, [P, P, P, L, I, P]),
-    "denet_solver_step": (I, [P, P, P, L, L, F, F, I, F, F, I, P]),
-    "denet_solver_adam": (I, [P, P, P, P, L, L, F, F, F, I, F, F, P]),
-    "denet_scale": (I, [P, L, F, P]),
-    "denet_grad_norm_chunk_len": (I, []),
-    "denet_grad_norm_check_table": (I, [P, I, I, L]),
-    "denet_grad_norm_workspace_bytes": (Z, [I, I]),
-    "denet_grad_norm": (I, [P, P, I, I, F, F, P, P, P, P, P]),
-    "denet_solver_step_coef": (I, [P, P, P, L, L, F, F, I, F, F, I, P, P]),
-    "denet_solver_adam_coef": (I, [P, P, P, P, L, L, F, F, F, I, F, F, P, P]),
-    "denet_ema_update": (I, [P, P, L, F, P]),
-    "denet_swap": (I, [P, P, L, P]),
-    "denet_corner_fwd": (I, [P, P] + [I] * 5 + [P]),
-    "denet_loss_workspace_bytes": (Z, []),
-    "denet_corner_loss": (I, [P] * 5 + [I] * 5 + [F, P]),
-    "denet_corner_loss_focal": (I, [P] * 5 + [I] * 5 + [F, F, P]),
-    "denet_sparse_fwd": (I, [P, P, P, P] + [I] * 10 + [P]),
-    "denet_sparse_sort_workspace_bytes": (Z, [I] * 5),
-    "denet_sparse_sort_is_single": (I, [I] * 5),
-    "denet_sparse_sort": (I, [P, P, Z] + [I] * 5 + [P]),
-    "denet_sparse_bwd": (I, [P, P, P, Z, P] + [I] * 10 + [P]),
-    "denet_sparse_bilinear_fwd": (I, [P] * 5 + [I] * 9 + [P]),
-    "denet_sparse_bilinear_workspace_bytes": (Z, [I] * 5),
-    "denet_sparse_bilinear_sort": (I, [P, P, Z] + [I] * 5 + [P]),
-    "denet_sparse_bilinear_bwd": (I, [P, P, P, P, Z, P] + [I] * 10 + [P]),
-    "denet_detect_loss": (I, [P] * 9 + [I] * 6 + [F, F, F, I, P]),
-    "denet_detect_loss_focal": (I, [P] * 9 + [I] * 6 + [F, F, F, I, F, P]),
-    "denet_detect_decode": (I, [P] * 5 + [I] * 6 + [F, P]),
-    "denet_detect_nms": (I, [P] * 5 + [I, I, I, F, F, P]),
-    "denet_soft_nms_batch_host": (L, [P, P, P, P, I, I, I, F, F, P, P, P, P, L]),
-    "denet_soft_nms_host": (I, [P, P, I, F, P, P, P]),
-    "denet_soft_nms_workspace_bytes": (Z, [I, I, I]),
-    "denet_soft_nms_batch": (I, [P, P, P, P, I, I, I, F, F, P, P, P, P, P, P, Z, P]),
-    "denet_build_samples_workspace_bytes": (Z, [I] * 6),
-    "denet_build_samples": (I, [P, P, P, P, P, Z] + [I] * 4 + [F, I, I, I, P]),
-    "denet_build_samples_stats": (I, [P, Z] + [I] * 6 + [P, P, P]),
-    "denet_edit_samples_device": (I, [P, P, I, I, P, L, L, P, P] + [I] * 4 + [P, P, P]),
-    "denet_host_cluster_samples": (I, [P, I, F, I, P, P]),
-    "denet_samples_finish_host": (I, [P, P, P, I, I, I, I, P]),
-    "denet_cluster_samples_workspace_bytes": (Z, [I, I]),
-    "denet_cluster_samples_device": (I, [P, P, P, I, I, F, I, I, I, P, P, P, P, Z, P]),
-}
+# every scalar type the header may use; any pointer is a c_void_p, the one other return type is `const char*`
+SCALARS = {"int": I, "long": L, "float": F, "double": D, "size_t": Z, "uint64_t": U64, "hipStream_t": P}
 
 
-class DenetHipError(RuntimeError):
-    pass
+def _ctype(decl, where, returns=False):
+    """ctypes type of one parameter `type name`, struct field `type name` or return type `type`. No default: what the map
+    does not hold raises and names the declaration."""
+    words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+    if returns and words == ["char", "*"]:
+        return ctypes.c_char_p
+    if "*" in words and not returns:
+        return P
+    kind = " ".join(words if returns else words[:-1])
+    if kind not in SCALARS:
+        raise DenetHipError("include/denet_hip.h: %s: no ctypes type for `%s`" % (where, decl.strip()))
+    return SCALARS[kind]
+
+
+def parse_header(text):
+    """C text of the header -> (signatures {name: (restype, argtypes)}, defines {name: int}, structs {name: fields}).
+    Strict: every `denet_<name>(` outside a comment has to be a whole `ret denet_<name>(args);` of known types."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(DENET_\w+)[ \t]*(.*?)[ \t]*$", text, re.M):
+        if value:                                        # (the include guard has none)
+            if not re.fullmatch(r"\(?-?\d+\)?", value):
+                raise DenetHipError("include/denet_hip.h: #define %s: `%s` is not an integer" % (name, value))
+            defines[name] = int(value.strip("()"))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    structs = {}
+
+    def take_struct(m):
+        fields = [f for f in m.group(2).split(";") if f.strip()]
+        structs[m.group(1)] = [(f.split()[-1].lstrip("*"), _ctype(f, "struct " + m.group(1))) for f in fields]
+        return ""
+    text = re.sub(r"typedef\s+struct\s+(denet_\w+)\s*\{([^}]*)\}\s*\1\s*;", take_struct, text)
+    signatures = {}
+    for statement in text.split(";"):
+        named = re.search(r"\b(denet_\w+)\s*\(", statement)
+        if not named:
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(denet_\w+)\s*\(([^()]*)\)\s*", statement)
+        if not m:
+            raise DenetHipError("include/denet_hip.h: %s: not one whole declaration `ret %s(args);`" % ((named.group(1),) * 2))
+        ret, name, args = m.groups()
+        if name in signatures:
+            raise DenetHipError("include/denet_hip.h: %s is declared twice" % name)
+        args = [] if args.strip() == "void" else args.split(",")
+        signatures[name] = (_ctype(ret, name, returns=True), [_ctype(a, name) for a in args])
+    return signatures, defines, structs
+
+
+def _read_header():
+    if not os.path.exists(HEADER_PATH):
+        raise DenetHipError("include/denet_hip.h is missing (%s): the binding is derived from it" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, argtypes) of every entry point; DENET_* -> value; the one struct that crosses the boundary, defined once
+SIGNATURES, DEFINES, _STRUCTS = _read_header()
+
+
+class BnLink(ctypes.Structure):
+    """denet_bn_link"""
+    _fields_ = _STRUCTS["denet_bn_link"]
 
 
 _lib = None

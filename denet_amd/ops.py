@@ -1554,12 +1554,7 @@ BWD_SUMS = int(os.environ.get("DENET_BN_BWD_SUMS", "3"))      # bit 0: Winograd 
 
 
 def _bn_link_struct(x, aux, y, gamma, beta, mean, invstd, coef, out, relu):
-    import ctypes
-
-    class _C(ctypes.Structure):
-        _fields_ = [(n, ctypes.c_void_p) for n in ("x", "aux", "y", "gamma", "beta", "mean", "invstd", "coef", "out")] + \
-                   [("relu", ctypes.c_int)]
-    return _C(ptr(x), ptr(aux), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(coef), ptr(out), int(relu))
+    return _lib.BnLink(ptr(x), ptr(aux), ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), ptr(coef), ptr(out), int(relu))
 
 
 class BnSums:
@@ -2188,7 +2183,7 @@ def relu_bwd(y, dy):
 
 
 # the smooth activations of csrc/activation.hip: name -> DENET_ACT_* (include/denet_hip.h)
-ACT_KINDS = {"sigmoid": 1, "tanh": 2, "elu": 3, "softplus": 4}
+ACT_KINDS = {kind: _lib.DEFINES["DENET_ACT_" + kind.upper()] for kind in ("sigmoid", "tanh", "elu", "softplus")}
 
 
 def act_fwd(x, c_logical, kind):

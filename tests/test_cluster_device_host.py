@@ -3,15 +3,14 @@ flags, the C-ABI surface, and the CLOSED FORM the kernels implement - restated h
 with the sequential apply_cluster of oracle/build_samples_naive.py (denet/layer/denet_sparse.cc:165-242) + the final ranking.
 tests/test_cluster_device_gpu.py imports the restatement for the device's tie rule."""
 import os
-import re
 
 import numpy as np
 import pytest
 
+import cabi
 from denet_amd import lib as dlib, ops, switches
 from oracle import build_samples_naive as NV
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 
 
@@ -126,17 +125,10 @@ def test_drivers_parse_device_cluster():
 def test_cabi_declares_the_cluster_entries():
     """include/denet_hip.h and lib.SIGNATURES agree on the new entries, argument by argument; the refusals answer before any device
     work"""
-    hdr = open(os.path.join(ROOT, "include", "denet_hip.h")).read()
-    kinds = {"int": dlib.I, "float": dlib.F, "size_t": dlib.Z, "hipStream_t": dlib.P}
     for name in ("denet_cluster_samples_workspace_bytes", "denet_cluster_samples_device"):
-        m = re.search(r"\n(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
+        _, restype, declared = cabi.declaration(name)
         res, args = dlib.SIGNATURES[name]
-        assert res is kinds[m.group(1)], name
-        declared = []
-        for a in m.group(2).split(","):
-            a = a.strip()
-            declared.append(dlib.P if "*" in a else kinds[a.replace("const ", "").split()[0]])
+        assert res is restype, name
         assert declared == list(args), (name, declared, args)
     L = dlib.load()
     assert L.denet_cluster_samples_workspace_bytes(2, 5760) >= 2 * 5760 * 40

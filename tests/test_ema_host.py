@@ -3,16 +3,15 @@ schedule, the validation of `ema_decay`, the driver flag, the naming of the aver
 with its refusals, and the recurrence restated in numpy float64. tests/test_ema_gpu.py imports `om_at`, `ema64`, `U` and `bound`."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 
+import cabi
 from denet_amd import lib as dlib, ops
 from denet_amd.model import model_cnn
 from denet_amd.model.model_cnn import ema_decay_at
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24            # unit roundoff of float32
 
 
@@ -134,15 +133,12 @@ NEW_ENTRIES = ("denet_ema_update", "denet_swap")
 def test_cabi_declares_the_new_entries():
     """include/denet_hip.h and lib.SIGNATURES agree argument by argument, the library exports the symbols, the header says that
     neither has a reference counterpart, and the profile kinds have names"""
-    hdr = open(os.path.join(ROOT, "include", "denet_hip.h")).read()
-    kinds = {"int": dlib.I, "float": dlib.F, "size_t": dlib.Z, "hipStream_t": dlib.P, "long": dlib.L}
+    hdr = open(cabi.HEADER).read()
     L = dlib.load()
     for name in NEW_ENTRIES:
-        m = re.search(r"\n(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
+        _, restype, declared = cabi.declaration(name)
         res, args = dlib.SIGNATURES[name]
-        assert res is kinds[m.group(1)], name
-        declared = [dlib.P if "*" in a else kinds[a.replace("const ", "").split()[0]] for a in (s.strip() for s in m.group(2).split(","))]
+        assert res is restype, name
         assert declared == list(args), (name, declared, args)
         assert hasattr(L, name)
     block = hdr[hdr.index("csrc/ema.hip"):hdr.index("int denet_swap")]

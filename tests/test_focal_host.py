@@ -2,17 +2,15 @@
 no GPU: the float64 reference checked against central differences of its own costs, the desc grammar, the JSON key, model-modify,
 the refusals and the C-ABI surface."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import cabi
 import focal_reference as FR
 from denet_amd import lib as dlib, ops
 from denet_amd.model import model_cnn, modify
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("denet_corner_loss_focal", "denet_detect_loss_focal")
 GAMMAS = [1.0, 2.0, 3.5]
 
@@ -202,21 +200,13 @@ def test_drivers_log_gamma_per_cost_layer():
 def test_cabi_declares_and_binds_the_two_entries():
     """include/denet_hip.h and lib.SIGNATURES agree argument by argument, the library exports the symbols, each declaration names
     the reference lines it extends, says that the reference has no such mode and names section 17"""
-    hdr = open(os.path.join(ROOT, "include", "denet_hip.h")).read()
-    kinds = {"int": dlib.I, "float": dlib.F, "size_t": dlib.Z, "hipStream_t": dlib.P}
     L = dlib.load()
     extends = {"denet_corner_loss_focal": "denet_corner.py:126-134", "denet_detect_loss_focal": "denet_detect.py:238-313"}
     for name in NAMES:
-        m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*\n(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr, re.S)
-        assert m, name
-        text = " ".join(w for w in m.group(1).split() if w != "*")
+        text, restype, declared = cabi.declaration(name)
         assert "no such mode" in text and "section 17" in text and extends[name] in text, name
         res, args = dlib.SIGNATURES[name]
-        assert res is kinds[m.group(2)], name
-        declared = []
-        for a in m.group(3).split(","):
-            a = a.strip()
-            declared.append(dlib.P if "*" in a else kinds[a.replace("const ", "").split()[0]])
+        assert res is restype, name
         assert declared == list(args), (name, declared, args)
         assert hasattr(L, name), name
         # the arguments of the plain entry plus `float gamma` in front of the stream

@@ -2,16 +2,14 @@
 GPU: the driver flags, the limit's validation, the chunk table of the reduction, the C-ABI surface with its refusals, and the
 contract's coefficient restated in numpy float64. tests/test_grad_clip_gpu.py imports RANGES, `laid_out` and `coef64`."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import cabi
 from denet_amd import lib as dlib, ops
 from denet_amd.model import model_cnn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CH = ops.NORM_CHUNK
 # 64, 192, exactly one chunk, one chunk + 64, five chunks + 192 floats
 LENGTHS = (64, 192, CH, CH + 64, 5 * CH + 192)
@@ -105,19 +103,10 @@ NEW_ENTRIES = ("denet_grad_norm_chunk_len", "denet_grad_norm_check_table", "dene
 def test_cabi_declares_the_new_entries():
     """include/denet_hip.h and lib.SIGNATURES agree on the new entries, argument by argument; the coef solvers are the plain
     signatures plus one pointer"""
-    hdr = open(os.path.join(ROOT, "include", "denet_hip.h")).read()
-    kinds = {"int": dlib.I, "float": dlib.F, "size_t": dlib.Z, "hipStream_t": dlib.P, "long": dlib.L}
     for name in NEW_ENTRIES:
-        m = re.search(r"\n(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
+        _, restype, declared = cabi.declaration(name)
         res, args = dlib.SIGNATURES[name]
-        assert res is kinds[m.group(1)], name
-        declared = []
-        for a in m.group(2).split(","):
-            a = a.strip()
-            if a == "void":
-                continue
-            declared.append(dlib.P if "*" in a else kinds[a.replace("const ", "").split()[0]])
+        assert res is restype, name
         assert declared == list(args), (name, declared, args)
     for plain in ("denet_solver_step", "denet_solver_adam"):
         a, b = dlib.SIGNATURES[plain][1], dlib.SIGNATURES[plain + "_coef"][1]

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import cabi
 from denet_amd import lib as dlib
 from denet_amd.common import json_util
 from denet_amd.model import model_cnn, modify, zoo
@@ -271,10 +272,16 @@ def test_host_helpers_match_imported_reference():
 
 
 def test_cabi_exports_every_declared_symbol():
-    """the shared library loads and exports exactly what include/denet_hip.h declares (no compute calls)"""
+    """the shared library loads and exports exactly what include/denet_hip.h declares (no compute calls), and the binding derived
+    from the header agrees with the second reading of it (tests/cabi.py) in every declaration's return and argument types"""
     hdr = open(os.path.join(ROOT, "include", "denet_hip.h")).read()
     declared = set(re.findall(r"\b(denet_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(dlib.SIGNATURES.keys()), declared ^ set(dlib.SIGNATURES.keys())
+    second = cabi.declarations()
+    assert set(second) == declared, declared ^ set(second)
+    for name, (_, restype, argtypes) in second.items():
+        res, args = dlib.SIGNATURES[name]
+        assert res is restype and list(args) == argtypes, (name, res, restype, args, argtypes)
     lib = dlib.load()
     for name in declared:
         assert hasattr(lib, name), name

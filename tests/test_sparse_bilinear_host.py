@@ -1,15 +1,13 @@
 """Opt-in bilinear RoI sampling of the DNS layer (tapRule 2, `DNS.I`; csrc/sparse_bilinear.hip), the part
 that needs no GPU: the desc tag, the JSON key, model-modify, the C-ABI surface and the refusals of the entry points."""
-import os
-import re
 
 import pytest
 
+import cabi
 from denet_amd import lib as dlib, ops
 from denet_amd.layer import denet_sparse as DS
 from denet_amd.model import model_cnn, modify
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("denet_sparse_bilinear_fwd", "denet_sparse_bilinear_workspace_bytes", "denet_sparse_bilinear_sort",
          "denet_sparse_bilinear_bwd")
 
@@ -81,20 +79,12 @@ def test_model_modify_sets_the_rule_and_takes_it_back():
 def test_cabi_declares_and_binds_the_four_entries():
     """include/denet_hip.h and lib.SIGNATURES agree argument by argument, the library exports the symbols, every declaration says that
     the reference has no counterpart and names section 16, and ops carries the three host functions and the two launch names"""
-    hdr = open(os.path.join(ROOT, "include", "denet_hip.h")).read()
-    kinds = {"int": dlib.I, "float": dlib.F, "size_t": dlib.Z, "hipStream_t": dlib.P}
     L = dlib.load()
     for name in NAMES:
-        m = re.search(r"/\*((?:(?!\*/).)*)\*/\s*\n(size_t|int)\s+%s\s*\(([^)]*)\)\s*;" % name, hdr, re.S)
-        assert m, name
-        text = " ".join(w for w in m.group(1).split() if w != "*")             # (the comment's line breaks and their " * ")
+        text, restype, declared = cabi.declaration(name)
         assert "no counterpart" in text and "section 16" in text, name
         res, args = dlib.SIGNATURES[name]
-        assert res is kinds[m.group(2)], name
-        declared = []
-        for a in m.group(3).split(","):
-            a = a.strip()
-            declared.append(dlib.P if "*" in a else kinds[a.replace("const ", "").split()[0]])
+        assert res is restype, name
         assert declared == list(args), (name, declared, args)
         assert hasattr(L, name), name
     for fn in ("sparse_bilinear_fwd", "sparse_bilinear_sort_async", "sparse_bilinear_bwd"):
