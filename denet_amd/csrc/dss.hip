@@ -6,21 +6,13 @@
 //   detection cost/gradient                          reference denet/layer/denet_detect.py:238-313,
 //                                                    denet/common/theano_util.py:27-34
 // This file is compiled with -ffp-contract=off: tap indices must be reproducible bit for bit.
-#include "common.h"
+// What the opt-in modes (focal.hip, sparse_bilinear.hip) compute in common with these kernels lives in dss.h: the finishing sum,
+// the detection cost behind its class part, the gather gradient's cell sum and the sort workspace's layout.
+#include "dss.h"
 #include "../../include/denet_hip.h"
 #include <stdlib.h>
-#include <math.h>
 
 namespace {
-
-constexpr double LN2 = 0.6931471805599453;
-
-int grid_for(long total) {
-    long b = (total + 255) / 256;
-    if (b > 8192) b = 8192;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 
 // ---------------------------------------------------------------------------------------------
 // corner map: conv[b,y,x,ci] -> corner_pr[b,k,ci,y,x], k=0: log P(no corner) from logit +x,
@@ -47,7 +39,6 @@ __global__ __launch_bounds__(256) void corner_fwd_kernel(const float* __restrict
 __global__ __launch_bounds__(256) void corner_loss_kernel(const float* __restrict__ pr, const float* __restrict__ tgt,
                                                           float* __restrict__ dconv, double* __restrict__ partial,
                                                           int B, int H, int W, int CP, int Cn, float scale) {
-    __shared__ double red[256];
     const long total = (long)B * H * W;
     const long plane = (long)H * W;
     double acc = 0;
@@ -65,27 +56,8 @@ __global__ __launch_bounds__(256) void corner_loss_kernel(const float* __restric
             }
         }
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-// out[slot] = factor * sum(partial[0..n))
-__global__ void finish_sum_kernel(const double* __restrict__ partial, int n, double factor, float* __restrict__ out) {
-    __shared__ double red[256];
-    double acc = 0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = (float)(factor * red[0]);
+    const double sum = block_sum_256(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -156,7 +128,7 @@ __global__ __launch_bounds__(256) void sparse_fwd_kernel(const float* __restrict
 //   sparse_scatter  one wave walks the chunk in slot order, 64 slots at a time; the lanes holding the same cell are
 //                   found with one ballot per key bit (no match-any instruction on gfx950), a lane's rank among them is
 //                   a popcount below its lane id, the lowest lane advances the cell's LDS cursor: stable by construction
-constexpr int SORT_CHUNK = 2048;
+// (SORT_CHUNK and the workspace these kernels share: dss.h, sort_layout)
 
 // workgroup (chunk, image), four waves: the histogram's 4 HW bytes of LDS are cleared and written out by all of them (one wave
 // took 2 x HW / 64 dependent rounds for it: 1.2 ms on the 128 x 128 map of DeNet-101 wide)
@@ -269,67 +241,13 @@ __global__ __launch_bounds__(256) void sparse_scatter_kernel(const int* __restri
     }
 }
 
-// gather gradient, step 2: one wave per feature-map cell sums the dy rows of every (roi, tap) that sampled this cell, in
-// ascending slot order (deterministic replacement for the reference's atomicAdd scatter)
+// gather gradient, step 2: one wave per feature-map cell sums the dy rows of the slots that sampled it (dss.h sparse_cell_sum)
 __global__ __launch_bounds__(256) void sparse_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ order,
                                                          const int* __restrict__ cell_start,
                                                          float* __restrict__ dfmap, int HW, int CP, int coff, int F,
                                                          int rois_per_image, int ntap, int KP, int zero_from,
                                                          long ncell_total) {
-    const int lane = threadIdx.x & 63;
-    const long cellg = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (cellg >= ncell_total) return;
-    const int b = (int)(cellg / HW);
-    const int cell = (int)(cellg - (long)b * HW);
-    const int n = rois_per_image * ntap;
-    const int F4 = F / 4;
-    const int epi = 64 / F4;  // entries per iteration
-    const int e = lane / F4, f4 = lane - e * F4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int* cs = cell_start + (long)b * (HW + 1);
-    const int start = cs[cell], end = cs[cell + 1];
-    const int* ord = order + (long)b * n;
-    // entry j of the cell belongs to lane group j % epi: a fixed left-to-right chain per group. The slots of up to CH entries come
-    // in with ONE coalesced load and are handed out by shuffles, and a group has the rows of four entries in flight before it
-    // adds them (in order): slot -> address -> row was two dependent loads per entry, 3-4 times in a row per wave - the kernel
-    // ran at the latency of that chain (281 us alone, 0.84 ms beside the first head layer's filter gradient)
-    const int CH = (64 / epi) * epi;
-    const bool grp = e < epi;
-    const float* dyb = dy + (long)b * rois_per_image * KP + f4 * 4;
-    for (int base = start; base < end; base += CH) {
-        const int cnt = min(CH, end - base);
-        const int mine = (lane < cnt) ? ord[base + lane] : 0;
-        for (int j0 = 0; j0 < cnt; j0 += 4 * epi) {
-            f32x4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * epi + e;
-                const int slot = __shfl(mine, j & 63, 64);
-                const int roi = slot / ntap, tap = slot - roi * ntap;
-                v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (grp && j < cnt) v[u] = *(const f32x4*)(dyb + (long)roi * KP + (long)tap * F);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (grp && j0 + u * epi + e < cnt) acc += v[u];
-        }
-    }
-    f32x4 tot = acc;
-    for (int k = 1; k < epi; ++k) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) tot[c] += __shfl(acc[c], f4 + k * F4, 64);
-    }
-    float* o = dfmap + cellg * CP;
-    if (lane < F4) {
-        if ((coff & 3) == 0) {
-            *(f32x4*)(o + coff + lane * 4) = tot;
-        } else {      // DNC.C: five corner channels in front of the features, the slice is not 16-byte aligned
-            float* q = o + coff + lane * 4;
-            q[0] = tot[0]; q[1] = tot[1]; q[2] = tot[2]; q[3] = tot[3];
-        }
-    }
-    // zero the physical padding channels of this cell
-    for (int c = zero_from + lane; c < CP; c += 64) o[c] = 0.f;
+    sparse_cell_sum<false>(dy, order, cell_start, nullptr, dfmap, HW, CP, coff, F, rois_per_image, ntap, KP, zero_from, ncell_total);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -347,7 +265,6 @@ __global__ __launch_bounds__(256) void detect_loss_kernel(const float* __restric
                                                           const float* __restrict__ roi_bbox,
                                                           const float* __restrict__ fit_t, int nfit, float fit_factor,
                                                           float fit_scale) {
-    __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int m = blockIdx.x * 4 + wv;
     double derr = 0, berr = 0;
@@ -377,100 +294,13 @@ __global__ __launch_bounds__(256) void detect_loss_kernel(const float* __restric
         }
         for (int o = 32; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
         derr = -(double)e * (double)inv_logn;
-        if (nreg > 0) {
-            float sl = 0.f;
-            if (lane < 4) {
-                const float valid = bbox_valid[m];
-                const float* bt = bbox_t + (long)m * 8;
-                const float reg = z[ncls + lane];
-                float d = 0.f, dd_dreg = -1.f;   // d = residual fed to smooth L1 ; dd_dreg = d(d)/d(reg)
-                if (!bounded_iou) {
-                    // Fast R-CNN targets: (tcx-scx)/sw, (tcy-scy)/sh, ln(tw/sw), ln(th/sh)
-                    float tk;
-                    if (lane < 2) tk = (bt[lane] - bt[4 + lane]) / bt[6 + lane];
-                    else tk = logf(bt[lane] / bt[4 + lane]);
-                    d = tk - reg;
-                    dd_dreg = -1.f;
-                } else {
-                    // bounded IoU (denet_detect.py:266-286); prediction decoded from the RoI box
-                    const float* rb = roi_bbox + (long)m * 4;
-                    const float scx = 0.5f * (rb[0] + rb[2]), scy = 0.5f * (rb[1] + rb[3]);
-                    const float sw = rb[2] - rb[0], sh = rb[3] - rb[1];
-                    const float eps = 0.001f;
-                    if (lane < 2) {
-                        const float sc = lane == 0 ? scx : scy, se_ = lane == 0 ? sw : sh;
-                        // predict_x = 0.5*((cx - w/2) + (cx + w/2)) -> cx = reg*extent + centre
-                        const float pc = reg * se_ + sc;
-                        const float dxy = bt[lane] - pc;
-                        const float tw = bt[2 + lane];
-                        if (dxy >= 0.f) {
-                            const float den = tw + dxy + eps;
-                            d = 2.f * dxy / den;
-                            // d/d(dxy) = 2*(tw+eps)/den^2 ; d(dxy)/dreg = -extent
-                            dd_dreg = 2.f * (tw + eps) / (den * den) * (-se_);
-                        } else {
-                            const float den = tw - dxy + eps;
-                            d = -2.f * dxy / den;
-                            dd_dreg = -2.f * (tw + eps) / (den * den) * (-se_);
-                        }
-                    } else {
-                        const float se_ = lane == 2 ? sw : sh;
-                        const float pw = expf(reg) * se_;
-                        const float tw = bt[lane];
-                        const float a = tw / (pw + eps), c2 = pw / (tw + eps);
-                        if (a <= c2) {
-                            d = 1.f - a;
-                            dd_dreg = tw / ((pw + eps) * (pw + eps)) * pw;   // d(1-a)/dpw * dpw/dreg
-                        } else {
-                            d = 1.f - c2;
-                            dd_dreg = -pw / (tw + eps);
-                        }
-                    }
-                }
-                const float ad = fabsf(d);
-                sl = (ad < 1.f) ? 0.5f * d * d : ad - 0.5f;
-                const float dsl = (ad < 1.f) ? d : (d > 0.f ? 1.f : -1.f);
-                if (dz) dz[ncls + lane] = bbox_scale * valid * dsl * dd_dreg;
-                sl *= valid;
-            }
-            for (int o = 2; o > 0; o >>= 1) sl += __shfl_xor(sl, o, 64);
-            berr = (double)bbox_factor * (double)bbox_factor * (double)sl;     // factor of get_errors :295 and of cost :310
-        }
-        if (nfit > 0) {
-            // independent fitness distribution (denet_detect.py:103-108, 298-301): a second soft-target cross entropy
-            // over the nfit logits behind the box regressors
-            const float* zf = z + ncls + nreg;
-            const float* tf = fit_t + (long)m * nfit;
-            const float zv = lane < nfit ? zf[lane] : -INFINITY;
-            float fm = zv;
-            for (int o = 32; o > 0; o >>= 1) fm = fmaxf(fm, __shfl_xor(fm, o, 64));
-            float fe = lane < nfit ? expf(zv - fm) : 0.f, ft = lane < nfit ? tf[lane] : 0.f;
-            float fse = fe, fts = ft;
-            for (int o = 32; o > 0; o >>= 1) {
-                fse += __shfl_xor(fse, o, 64);
-                fts += __shfl_xor(fts, o, 64);
-            }
-            const float flse = logf(fse);
-            const float finv = (float)(1.0 / log((double)nfit));
-            const float flp = lane < nfit ? (zv - fm) - flse : 0.f;
-            float fsum = ft * flp;
-            if (dz && lane < nfit) dz[ncls + nreg + lane] = fit_scale * finv * (fts * expf(flp) - ft);
-            for (int o = 32; o > 0; o >>= 1) fsum += __shfl_xor(fsum, o, 64);
-            berr += (double)fit_factor * (-(double)fsum * (double)finv);
-        }
+        if (nreg > 0) berr = detect_box_term(z, dz, m, lane, ncls, bbox_valid, bbox_t, roi_bbox, bounded_iou, bbox_factor, bbox_scale);
+        if (nfit > 0) berr += detect_fit_term(z, dz, m, lane, ncls, nreg, fit_t, nfit, fit_factor, fit_scale);
         if (dz) {
             for (int c = ncls + nreg + nfit + lane; c < CP; c += 64) dz[c] = 0.f;
         }
     }
-    if (lane == 0) {
-        red[0][wv] = derr;
-        red[1][wv] = berr;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[gridDim.x + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+    detect_store_sums(derr, berr, partial);
 }
 
 }  // namespace
@@ -490,8 +320,7 @@ extern "C" int denet_corner_loss(const float* corner_pr, const float* target, fl
                                  void* workspace, int B, int H, int W, int CP, int Cn, float cost_factor,
                                  hipStream_t stream) {
     DENET_CHECK_ARG(corner_pr && target && cost && workspace && Cn > 0, "corner_loss: bad args");
-    int g = grid_for((long)B * H * W);
-    if (g > 1024) g = 1024;
+    const int g = corner_loss_grid((long)B * H * W);
     const float scale = (float)((double)cost_factor / ((double)B * LN2));
     hipLaunchKernelGGL(corner_loss_kernel, dim3(g), dim3(256), 0, stream, corner_pr, target, dconv, (double*)workspace,
                        B, H, W, CP, Cn, scale);
@@ -599,28 +428,6 @@ __global__ __launch_bounds__(1024) void sparse_sort_image_kernel(const int* __re
         if (live) o[start + rank] = i;
     }
 }
-
-// Workspace of denet_sparse_sort / denet_sparse_bwd: order [B][n] | cell_start [B][HW+1] | counts [B][nchunk][HW] |
-// positions [B][nchunk][HW] (int32)
-namespace {
-struct SortLayout {
-    int n, HW, nchunk, key_bits;
-    size_t off_start, off_table, total;   // in ints
-};
-int sort_layout(int B, int H, int W, int rois_per_image, int gs, SortLayout* L) {
-    DENET_CHECK_ARG(B > 0 && H > 0 && W > 0 && rois_per_image > 0 && gs > 0, "sparse_sort: bad arguments");
-    DENET_CHECK_ARG((long)H * W <= 32768, "sparse_sort: feature map of %d x %d cells exceeds the 32768-cell LDS cursor", H, W);
-    L->n = rois_per_image * gs * gs;
-    L->HW = H * W;
-    L->nchunk = (L->n + SORT_CHUNK - 1) / SORT_CHUNK;
-    L->key_bits = 1;
-    while ((1 << L->key_bits) < L->HW) L->key_bits++;
-    L->off_start = (size_t)B * L->n;
-    L->off_table = L->off_start + (size_t)B * (L->HW + 1);
-    L->total = L->off_table + (size_t)2 * B * L->nchunk * L->HW;      // counts | positions
-    return DENET_OK;
-}
-}  // namespace
 
 extern "C" size_t denet_sparse_sort_workspace_bytes(int B, int H, int W, int rois_per_image, int gs) {
     SortLayout L;

@@ -3,15 +3,12 @@
 //   corner NLL cost/gradient      reference denet/layer/denet_corner.py:126-134   (dss.hip corner_loss_kernel)
 //   detection cost/gradient       reference denet/layer/denet_detect.py:238-313   (dss.hip detect_loss_kernel)
 // whose kernels and entry points stay as they are; gamma = 0 gives their formulas.
-// This file is compiled with -ffp-contract=off like dss.hip: the box regression and independent-fitness terms are the plain
-// kernel's statements and must give its bits.
-#include "common.h"
+// This file is compiled with -ffp-contract=off like dss.hip: the box regression and independent-fitness terms, the finishing
+// sum and the corner grid are the plain kernels' own code (dss.h) and give their bits.
+#include "dss.h"
 #include "../../include/denet_hip.h"
-#include <math.h>
 
 namespace {
-
-constexpr double LN2 = 0.6931471805599453;
 
 // gamma is 0 (the plain cost) or finite and >= 1: q^(gamma - 1) is singular in between
 bool gamma_ok(float gamma) { return gamma == 0.f || (isfinite(gamma) && gamma >= 1.f); }
@@ -25,7 +22,6 @@ bool gamma_ok(float gamma) { return gamma == 0.f || (isfinite(gamma) && gamma >=
 __global__ __launch_bounds__(256) void corner_focal_loss_kernel(const float* __restrict__ pr, const float* __restrict__ tgt,
                                                                 float* __restrict__ dconv, double* __restrict__ partial,
                                                                 int B, int H, int W, int CP, int Cn, float scale, float gamma) {
-    __shared__ double red[256];
     const long total = (long)B * H * W;
     const long plane = (long)H * W;
     double acc = 0;
@@ -46,28 +42,8 @@ __global__ __launch_bounds__(256) void corner_focal_loss_kernel(const float* __r
             }
         }
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-// out[0] = factor * sum(partial[0..n)) in a fixed order (the finishing pass of the plain costs, dss.hip)
-__global__ __launch_bounds__(256) void focal_finish_sum_kernel(const double* __restrict__ partial, int n, double factor,
-                                                               float* __restrict__ out) {
-    __shared__ double red[256];
-    double acc = 0;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = (float)(factor * red[0]);
+    const double sum = block_sum_256(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
 // w = q^gamma and q^(gamma - 1) from one powf. gamma = 0: w = 1 for every q, q = 0 included, and the second factor only ever
@@ -86,8 +62,8 @@ __device__ __forceinline__ void focal_factors(float q, float gamma, float& w, fl
 // detection cost, one wave per RoI. Class part (lp = log-softmax, p = exp(lp), q = 1 - p = -expm1(lp)):
 //   det_err = -sum_c t_c q_c^g lp_c / ln(ncls)
 //   a_c     = t_c * (q_c^g - g q_c^(g-1) p_c lp_c),  A = sum_c a_c,   dz_j = det_scale / ln(ncls) * (p_j * A - a_j)
-// The box regression, the independent-fitness cross entropy, costs[1] and the zeroed padding columns are
-// detect_loss_kernel's, statement for statement.
+// The box regression, the independent-fitness cross entropy (no focal factor) and costs[1] are detect_loss_kernel's: both
+// kernels call dss.h for them.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void detect_focal_loss_kernel(const float* __restrict__ logits, const float* __restrict__ det_t,
                                                                 const float* __restrict__ bbox_valid,
@@ -98,7 +74,6 @@ __global__ __launch_bounds__(256) void detect_focal_loss_kernel(const float* __r
                                                                 const float* __restrict__ roi_bbox,
                                                                 const float* __restrict__ fit_t, int nfit, float fit_factor,
                                                                 float fit_scale, float gamma) {
-    __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int m = blockIdx.x * 4 + wv;
     double derr = 0, berr = 0;
@@ -140,97 +115,13 @@ __global__ __launch_bounds__(256) void detect_focal_loss_kernel(const float* __r
                 dz[c] = det_scale * inv_logn * (p * A - a);
             }
         }
-        if (nreg > 0) {
-            float sl = 0.f;
-            if (lane < 4) {
-                const float valid = bbox_valid[m];
-                const float* bt = bbox_t + (long)m * 8;
-                const float reg = z[ncls + lane];
-                float d = 0.f, dd_dreg = -1.f;   // d = residual fed to smooth L1 ; dd_dreg = d(d)/d(reg)
-                if (!bounded_iou) {
-                    // Fast R-CNN targets: (tcx-scx)/sw, (tcy-scy)/sh, ln(tw/sw), ln(th/sh)
-                    float tk;
-                    if (lane < 2) tk = (bt[lane] - bt[4 + lane]) / bt[6 + lane];
-                    else tk = logf(bt[lane] / bt[4 + lane]);
-                    d = tk - reg;
-                    dd_dreg = -1.f;
-                } else {
-                    // bounded IoU (denet_detect.py:266-286); prediction decoded from the RoI box
-                    const float* rb = roi_bbox + (long)m * 4;
-                    const float scx = 0.5f * (rb[0] + rb[2]), scy = 0.5f * (rb[1] + rb[3]);
-                    const float sw = rb[2] - rb[0], sh = rb[3] - rb[1];
-                    const float eps = 0.001f;
-                    if (lane < 2) {
-                        const float sc = lane == 0 ? scx : scy, se_ = lane == 0 ? sw : sh;
-                        const float pc = reg * se_ + sc;
-                        const float dxy = bt[lane] - pc;
-                        const float tw = bt[2 + lane];
-                        if (dxy >= 0.f) {
-                            const float den = tw + dxy + eps;
-                            d = 2.f * dxy / den;
-                            dd_dreg = 2.f * (tw + eps) / (den * den) * (-se_);
-                        } else {
-                            const float den = tw - dxy + eps;
-                            d = -2.f * dxy / den;
-                            dd_dreg = -2.f * (tw + eps) / (den * den) * (-se_);
-                        }
-                    } else {
-                        const float se_ = lane == 2 ? sw : sh;
-                        const float pw = expf(reg) * se_;
-                        const float tw = bt[lane];
-                        const float a = tw / (pw + eps), c2 = pw / (tw + eps);
-                        if (a <= c2) {
-                            d = 1.f - a;
-                            dd_dreg = tw / ((pw + eps) * (pw + eps)) * pw;
-                        } else {
-                            d = 1.f - c2;
-                            dd_dreg = -pw / (tw + eps);
-                        }
-                    }
-                }
-                const float ad = fabsf(d);
-                sl = (ad < 1.f) ? 0.5f * d * d : ad - 0.5f;
-                const float dsl = (ad < 1.f) ? d : (d > 0.f ? 1.f : -1.f);
-                if (dz) dz[ncls + lane] = bbox_scale * valid * dsl * dd_dreg;
-                sl *= valid;
-            }
-            for (int o = 2; o > 0; o >>= 1) sl += __shfl_xor(sl, o, 64);
-            berr = (double)bbox_factor * (double)bbox_factor * (double)sl;     // factor of get_errors :295 and of cost :310
-        }
-        if (nfit > 0) {
-            // independent fitness distribution (denet_detect.py:103-108, 298-301): plain cross entropy, no focal factor
-            const float* zf = z + ncls + nreg;
-            const float* tf = fit_t + (long)m * nfit;
-            const float zv = lane < nfit ? zf[lane] : -INFINITY;
-            float fm = zv;
-            for (int o = 32; o > 0; o >>= 1) fm = fmaxf(fm, __shfl_xor(fm, o, 64));
-            float fe = lane < nfit ? expf(zv - fm) : 0.f, ft = lane < nfit ? tf[lane] : 0.f;
-            float fse = fe, fts = ft;
-            for (int o = 32; o > 0; o >>= 1) {
-                fse += __shfl_xor(fse, o, 64);
-                fts += __shfl_xor(fts, o, 64);
-            }
-            const float flse = logf(fse);
-            const float finv = (float)(1.0 / log((double)nfit));
-            const float flp = lane < nfit ? (zv - fm) - flse : 0.f;
-            float fsum = ft * flp;
-            if (dz && lane < nfit) dz[ncls + nreg + lane] = fit_scale * finv * (fts * expf(flp) - ft);
-            for (int o = 32; o > 0; o >>= 1) fsum += __shfl_xor(fsum, o, 64);
-            berr += (double)fit_factor * (-(double)fsum * (double)finv);
-        }
+        if (nreg > 0) berr = detect_box_term(z, dz, m, lane, ncls, bbox_valid, bbox_t, roi_bbox, bounded_iou, bbox_factor, bbox_scale);
+        if (nfit > 0) berr += detect_fit_term(z, dz, m, lane, ncls, nreg, fit_t, nfit, fit_factor, fit_scale);
         if (dz) {
             for (int c = ncls + nreg + nfit + lane; c < CP; c += 64) dz[c] = 0.f;
         }
     }
-    if (lane == 0) {
-        red[0][wv] = derr;
-        red[1][wv] = berr;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[blockIdx.x] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        partial[gridDim.x + blockIdx.x] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    }
+    detect_store_sums(derr, berr, partial);
 }
 
 }  // namespace
@@ -243,16 +134,14 @@ extern "C" int denet_corner_loss_focal(const float* corner_pr, const float* targ
     // (CP is the channel stride of dconv: it means nothing without one, the test-mode cost)
     DENET_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cn > 0 && (!dconv || Cn <= CP),
                     "corner_loss_focal: bad shape (B = %d, map %d x %d, Cn = %d, CP = %d)", B, H, W, Cn, CP);
-    // the grid of denet_corner_loss: at most 1024 partial sums, far inside denet_loss_workspace_bytes()
-    long g = ((long)B * H * W + 255) / 256;
-    if (g > 1024) g = 1024;
+    const int g = corner_loss_grid((long)B * H * W);
     const float scale = (float)((double)cost_factor / ((double)B * LN2));
     // ops.kernel_symbol: kind 70 = the corner cost, 71 = the detection cost
     const int prof = denet_prof_begin(70, 0, 0, 0, stream);
-    hipLaunchKernelGGL(corner_focal_loss_kernel, dim3((unsigned)g), dim3(256), 0, stream, corner_pr, target, dconv,
+    hipLaunchKernelGGL(corner_focal_loss_kernel, dim3(g), dim3(256), 0, stream, corner_pr, target, dconv,
                        (double*)workspace, B, H, W, CP, Cn, scale, gamma);
     denet_prof_end(prof, stream);
-    hipLaunchKernelGGL(focal_finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)workspace, (int)g,
+    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)workspace, g,
                        -(double)cost_factor / ((double)B * LN2), cost);
     DENET_CHECK_LAUNCH("corner_loss_focal");
     return DENET_OK;
@@ -282,10 +171,10 @@ extern "C" int denet_detect_loss_focal(const float* logits, const float* det_tar
                        dlogits, (double*)workspace, M, CP, ncls, nreg, det_scale, bbox_factor, bbox_scale, bounded_iou,
                        roi_bbox, fit_target, nfit, fit_factor, fit_factor / (float)batch, gamma);
     denet_prof_end(prof, stream);
-    hipLaunchKernelGGL(focal_finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)workspace, g,
+    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)workspace, g,
                        (double)cost_factor / (double)batch, costs);
     // costs[1] = box cost + independent-fitness cost (both already carry their factors)
-    hipLaunchKernelGGL(focal_finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)workspace + g, g,
+    hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, stream, (const double*)workspace + g, g,
                        1.0 / (double)batch, costs + 1);
     DENET_CHECK_LAUNCH("detect_loss_focal");
     return DENET_OK;

@@ -4,8 +4,9 @@
 //   sparse_bilinear_bwd_kernel   a cell sums weight * dy row over the (roi, tap, corner) slots that read it, in ascending slot order
 // The slots are grouped by cell with the counting sort of dss.hip (denet_sparse_sort sees n keys per image and nothing else; it is
 // called with 4 * rois_per_image): no second sort, no floating-point atomics, bit-identical from run to run.
+// The gradient kernel's body and the sort workspace's layout are the default path's own (dss.h).
 // This file is compiled with -ffp-contract=off: coordinates, weights and sums are defined operation by operation.
-#include "common.h"
+#include "dss.h"
 #include "../../include/denet_hip.h"
 #include <limits.h>
 
@@ -90,69 +91,15 @@ __global__ __launch_bounds__(256) void sparse_bilinear_fwd_kernel(const float* _
         o[k] = (k == ntap * F) ? bh : (k == ntap * F + 1) ? bw : 0.f;
 }
 
-// One wave per feature-map cell, the structure of sparse_bwd_kernel (dss.hip): entry j of the cell's list belongs to lane group
-// j % epi, epi = 64 / (F / 4); a group adds weight * row (the product rounded, then the sum) left to right from +0; the groups are
-// added in order. A slot s' = (roi * ntap + tap) * 4 + q names its dy row by s' >> 2 and its weight by wts4[s']. One lane loads
-// the slot AND its weight for up to CH entries (the dependent load is per chunk, not per entry); both are handed out by shuffles.
+// One wave per feature-map cell: sparse_bwd_kernel's cell sum (dss.h sparse_cell_sum) with a weight per slot. Entry j of the cell's
+// list belongs to lane group j % epi, epi = 64 / (F / 4); a group adds weight * row (the product rounded, then the sum) left to
+// right from +0; the groups are added in order.
 __global__ __launch_bounds__(256) void sparse_bilinear_bwd_kernel(const float* __restrict__ dy, const int* __restrict__ order,
                                                                   const int* __restrict__ cell_start,
                                                                   const float* __restrict__ wts4, float* __restrict__ dfmap,
                                                                   int HW, int CP, int coff, int F, int rois_per_image, int ntap,
                                                                   int KP, int zero_from, long ncell_total) {
-    const int lane = threadIdx.x & 63;
-    const long cellg = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (cellg >= ncell_total) return;
-    const int b = (int)(cellg / HW);
-    const int cell = (int)(cellg - (long)b * HW);
-    const int n = rois_per_image * ntap * 4;
-    const int F4 = F / 4;
-    const int epi = 64 / F4;  // entries per iteration
-    const int e = lane / F4, f4 = lane - e * F4;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    const int* cs = cell_start + (long)b * (HW + 1);
-    const int start = cs[cell], end = cs[cell + 1];
-    const int* ord = order + (long)b * n;
-    const float* wt = wts4 + (long)b * n;
-    const int CH = (64 / epi) * epi;
-    const bool grp = e < epi;
-    const float* dyb = dy + (long)b * rois_per_image * KP + f4 * 4;
-    for (int base = start; base < end; base += CH) {
-        const int cnt = min(CH, end - base);
-        const int mine = (lane < cnt) ? ord[base + lane] : 0;
-        const float wmine = (lane < cnt) ? wt[mine] : 0.f;
-        for (int j0 = 0; j0 < cnt; j0 += 4 * epi) {
-            f32x4 v[4];
-            float w[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + u * epi + e;
-                const int slot = __shfl(mine, j & 63, 64) >> 2;
-                w[u] = __shfl(wmine, j & 63, 64);
-                const int roi = slot / ntap, tap = slot - roi * ntap;
-                v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (grp && j < cnt) v[u] = *(const f32x4*)(dyb + (long)roi * KP + (long)tap * F);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (grp && j0 + u * epi + e < cnt) acc += w[u] * v[u];
-        }
-    }
-    f32x4 tot = acc;
-    for (int k = 1; k < epi; ++k) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) tot[c] += __shfl(acc[c], f4 + k * F4, 64);
-    }
-    float* o = dfmap + cellg * CP;
-    if (lane < F4) {
-        if ((coff & 3) == 0) {
-            *(f32x4*)(o + coff + lane * 4) = tot;
-        } else {      // DNC.C: five corner channels in front of the features, the slice is not 16-byte aligned
-            float* q = o + coff + lane * 4;
-            q[0] = tot[0]; q[1] = tot[1]; q[2] = tot[2]; q[3] = tot[3];
-        }
-    }
-    // zero the physical padding channels of this cell
-    for (int c = zero_from + lane; c < CP; c += 64) o[c] = 0.f;
+    sparse_cell_sum<true>(dy, order, cell_start, wts4, dfmap, HW, CP, coff, F, rois_per_image, ntap, KP, zero_from, ncell_total);
 }
 
 // the expanded list (four slots per tap) in the terms of denet_sparse_sort: rois_per_image * 4 "RoIs" of gs * gs keys
@@ -218,20 +165,20 @@ extern "C" int denet_sparse_bilinear_bwd(const float* dy, const int* taps4, cons
     DENET_CHECK_ARG(coff >= 0 && KP >= gs * gs * F + 2, "sparse_bilinear_bwd: channel layout inconsistent");
     DENET_CHECK_ARG(zero_from >= coff + F && zero_from <= CP, "sparse_bilinear_bwd: zero_from out of range");
     DENET_CHECK_ARG(dy && wts4 && sort_ws && dfmap, "sparse_bilinear_bwd: null pointer");
-    const size_t need = denet_sparse_sort_workspace_bytes(B, H, W, rois4, gs);
-    DENET_CHECK_ARG(need > 0 && sort_ws_bytes >= need, "sparse_bilinear_bwd: workspace too small (%zu < %zu)", sort_ws_bytes, need);
+    SortLayout L;
+    rc = sort_layout(B, H, W, rois4, gs, &L);      // (cannot fail behind expanded_rois)
+    if (rc) return rc;
+    const size_t need = L.total * sizeof(int);
+    DENET_CHECK_ARG(sort_ws_bytes >= need, "sparse_bilinear_bwd: workspace too small (%zu < %zu)", sort_ws_bytes, need);
     if (taps4) {
         rc = denet_sparse_sort(taps4, sort_ws, sort_ws_bytes, B, H, W, rois4, gs, stream);
         if (rc) return rc;
     }
-    // layout of denet_sparse_sort's workspace (dss.hip): order [B][n'] | cell_start [B][HW + 1] | ...
-    const int ntap = gs * gs;
     const int* order = (const int*)sort_ws;
-    const int* cell_start = order + (size_t)B * rois4 * ntap;
     const long ncell = (long)B * H * W;
     const int prof = denet_prof_begin(61, 0, 0, 0, stream);
-    hipLaunchKernelGGL(sparse_bilinear_bwd_kernel, dim3((unsigned)((ncell + 3) / 4)), dim3(256), 0, stream, dy, order, cell_start,
-                       wts4, dfmap, H * W, CP, coff, F, rois_per_image, ntap, KP, zero_from, ncell);
+    hipLaunchKernelGGL(sparse_bilinear_bwd_kernel, dim3((unsigned)((ncell + 3) / 4)), dim3(256), 0, stream, dy, order,
+                       order + L.off_start, wts4, dfmap, H * W, CP, coff, F, rois_per_image, gs * gs, KP, zero_from, ncell);
     denet_prof_end(prof, stream);
     DENET_CHECK_LAUNCH("sparse_bilinear_bwd");
     return DENET_OK;

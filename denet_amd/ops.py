@@ -2374,27 +2374,33 @@ def sparse_fwd(fmap, bbox, coff, F, rois_per_image, gs, kp, tap_rule=0, buffers=
 _SORT_STREAM = None
 
 
-def sparse_sort_async(taps, B, H, W, rois_per_image, gs):
-    """queues the tap sort of the gather gradient on a side stream right after the forward gather (it needs only the
-    taps); returns the event sparse_bwd(presorted=...) waits for"""
+def _sort_async(sort, name, taps, ws, B, H, W, rois_per_image, gs, slots=1):
+    """queues `sort` (denet_sparse_sort or its bilinear form, `slots` keys per tap) for the tap list and returns the event the
+    gather gradient waits for"""
     global _SORT_STREAM
     if _SORT_STREAM is None:
         init_streams()
-    ws = WS.get("sparse_sort", _L().denet_sparse_sort_workspace_bytes(B, H, W, rois_per_image, gs))
-    if bool(_L().denet_sparse_sort_is_single(B, H, W, rois_per_image, gs)):
+    if bool(_L().denet_sparse_sort_is_single(B, H, W, rois_per_image * slots, gs)):
         # the one-kernel sort (one 1024-thread workgroup per image, 128 KB of LDS): on a side stream its workgroups starve for
         # LDS beside the head's matrix kernels until those drain (1.5-1.9 ms in the trace); alone it takes ~50 us, so it runs
         # here, on the compute stream, right behind the gather
-        check(_L().denet_sparse_sort(ptr(taps), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()), "sparse_sort")
+        check(sort(ptr(taps), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()), name)
         ev = torch.cuda.Event()
         ev.record()
         return ev
-    _SORT_STREAM.wait_stream(torch.cuda.current_stream())          # taps are written by sparse_fwd on this stream
+    _SORT_STREAM.wait_stream(torch.cuda.current_stream())          # the taps are written by the forward gather on this stream
     with torch.cuda.stream(_SORT_STREAM):
-        check(_L().denet_sparse_sort(ptr(taps), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()), "sparse_sort")
+        check(sort(ptr(taps), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()), name)
         ev = torch.cuda.Event()
         ev.record(_SORT_STREAM)
     return ev
+
+
+def sparse_sort_async(taps, B, H, W, rois_per_image, gs):
+    """queues the tap sort of the gather gradient on a side stream right after the forward gather (it needs only the
+    taps); returns the event sparse_bwd(presorted=...) waits for"""
+    ws = WS.get("sparse_sort", _L().denet_sparse_sort_workspace_bytes(B, H, W, rois_per_image, gs))
+    return _sort_async(_L().denet_sparse_sort, "sparse_sort", taps, ws, B, H, W, rois_per_image, gs)
 
 
 def sparse_bwd(dy, taps, dfmap, coff, F, rois_per_image, gs, zero_from, presorted=None):
@@ -2434,23 +2440,8 @@ def _sparse_bilinear_ws(B, H, W, rois_per_image, gs):
 def sparse_bilinear_sort_async(taps4, B, H, W, rois_per_image, gs):
     """sparse_sort_async for the expanded slot list of the bilinear rule (four slots per tap): the one-kernel form stays on the
     compute stream, the three-kernel form goes to the side stream; returns the event sparse_bilinear_bwd(presorted=...) waits for"""
-    global _SORT_STREAM
-    if _SORT_STREAM is None:
-        init_streams()
     ws = _sparse_bilinear_ws(B, H, W, rois_per_image, gs)
-    if bool(_L().denet_sparse_sort_is_single(B, H, W, rois_per_image * 4, gs)):
-        check(_L().denet_sparse_bilinear_sort(ptr(taps4), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()),
-              "sparse_bilinear_sort")
-        ev = torch.cuda.Event()
-        ev.record()
-        return ev
-    _SORT_STREAM.wait_stream(torch.cuda.current_stream())          # taps4 is written by sparse_bilinear_fwd on this stream
-    with torch.cuda.stream(_SORT_STREAM):
-        check(_L().denet_sparse_bilinear_sort(ptr(taps4), ptr(ws), ws.numel(), B, H, W, rois_per_image, gs, stream_ptr()),
-              "sparse_bilinear_sort")
-        ev = torch.cuda.Event()
-        ev.record(_SORT_STREAM)
-    return ev
+    return _sort_async(_L().denet_sparse_bilinear_sort, "sparse_bilinear_sort", taps4, ws, B, H, W, rois_per_image, gs, slots=4)
 
 
 def sparse_bilinear_bwd(dy, taps4, wts4, dfmap, coff, F, rois_per_image, gs, zero_from, presorted=None):
