@@ -6,34 +6,15 @@
 // All kernels are HBM-bound. Thread mapping: a thread owns one float4 of channels (c4) and walks
 // rows; LC = gcd(C/4, 256) lanes cover consecutive channels so a wave reads >= 256 contiguous bytes.
 // Per-channel reductions are accumulated in fp64 per thread, combined through LDS, written as
-// per-workgroup partials and finished by a second tiny kernel: deterministic, no atomics.
-#include "common.h"
+// per-workgroup partials and finished by a second tiny kernel: deterministic, no atomics. The order of both stages is
+// bn_reduce.h's, shared with every other reader and writer of such partials.
+#include "bn_reduce.h"
 #include "../../include/denet_hip.h"
 #include <stdlib.h>
 
 namespace {
 
-struct BnMap {
-    int LC;      // lanes along channels (float4 units)
-    int RS;      // rows handled concurrently by one workgroup
-    int gx, gy;  // grid
-};
-
-BnMap bn_map(long M, int C) {
-    BnMap m;
-    int c4 = C / 4;
-    int lc = 1;
-    while (lc < 256 && (c4 % (lc * 2)) == 0) lc *= 2;
-    m.LC = lc;
-    m.RS = 256 / lc;
-    m.gx = c4 / lc;
-    long rows_blocks = (M + m.RS - 1) / m.RS;
-    int gy = 1024 / m.gx;   // ~4 workgroups per CU; keeps the second-stage reduction short
-    if (gy < 1) gy = 1;
-    if (gy > rows_blocks) gy = (int)rows_blocks;
-    m.gy = gy;
-    return m;
-}
+constexpr int BN_WGS = 1024;    // bn_map's target: ~4 workgroups per CU; keeps the second-stage reduction short
 
 // ---- a max pool directly behind a BN + ReLU layer (the ResNet stem: convolution.py -> batch_norm_relu.py -> pool.py:38) ----
 // Forward: y = relu(bn(x)) is never written - the pooled maximum (and its argmax tap, pool.hip's rule: first maximum in scan
@@ -100,75 +81,23 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const float* __re
             ss[k] += d * d;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        red[tid * 8 + k] = s[k];
-        red[tid * 8 + 4 + k] = ss[k];
-    }
-    __syncthreads();
-    if (rsub == 0) {
-        for (int j = 1; j < RS; ++j) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                s[k] += red[(j * LC + cl) * 8 + k];
-                ss[k] += red[(j * LC + cl) * 8 + 4 + k];
-            }
-        }
-        double* p = partial + (long)blockIdx.y * 2 * C;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            p[c + k] = s[k];
-            p[C + c + k] = ss[k];
-        }
-    }
+    bn_reduce_workgroup_tail(s, ss, red, LC, C, c, partial);
 }
 
-// second stage: a one-wave workgroup reduces FC channels, FJ = 64/FC lanes stride over the partial rows and a shuffle tree
-// adds them. The stage is latency bound (a few hundred KB, a chain of dependent row loads per lane): 32 row lanes keep the
-// chain at gy/128 rounds of 4 loads in flight, C/2 workgroups spread it over the chip. NO LDS on purpose: these kernels run
-// beside the persistent 64-channel Winograd kernels, whose workgroups hold a CU's whole LDS - a kernel that asks for any
-// waits for one of them to retire (measured: 165 us instead of 7 for the six layer-1 finals of a step).
-constexpr int FC = 2, FJ = 64 / FC, FINAL_NT = 64;
-__device__ __forceinline__ void reduce_row_lanes(double& s, double& ss) {
-#pragma unroll
-    for (int off = FC; off < 64; off <<= 1) {
-        s += __shfl_xor(s, off, 64);
-        ss += __shfl_xor(ss, off, 64);
-    }
-}
-__device__ __forceinline__ void reduce_partials(const double* __restrict__ partial, int gy, int C, int c, int jl,
-                                                double& s, double& ss) {
-    s = 0;
-    ss = 0;
-    if (c < C) {
-        int j = jl;
-        // 4 independent row loads in flight per lane
-        for (; j + 3 * FJ < gy; j += 4 * FJ) {
-            const double a0 = partial[(long)j * 2 * C + c], b0 = partial[(long)j * 2 * C + C + c];
-            const double a1 = partial[(long)(j + FJ) * 2 * C + c], b1 = partial[(long)(j + FJ) * 2 * C + C + c];
-            const double a2 = partial[(long)(j + 2 * FJ) * 2 * C + c], b2 = partial[(long)(j + 2 * FJ) * 2 * C + C + c];
-            const double a3 = partial[(long)(j + 3 * FJ) * 2 * C + c], b3 = partial[(long)(j + 3 * FJ) * 2 * C + C + c];
-            s += (a0 + a1) + (a2 + a3);
-            ss += (b0 + b1) + (b2 + b3);
-        }
-        for (; j < gy; j += FJ) {
-            s += partial[(long)j * 2 * C + c];
-            ss += partial[(long)j * 2 * C + C + c];
-        }
-    }
-}
+// second stage (bn_reduce.h): one wave of FINAL_NT threads per BNF_FC channels, no LDS
+constexpr int FINAL_NT = 64;
 
 // first of two stages for long partial lists (a stem convolution leaves 16 384 rows = 16 MB, which the C/8 workgroups of the
 // final kernel would walk alone): slice `blockIdx.y` of the rows -> out[slice][2][C]
 __global__ __launch_bounds__(FINAL_NT) void bn_stats_fold_kernel(const double* __restrict__ partial, int gy, int per, int C,
                                                                  double* __restrict__ out) {
-    const int cl = threadIdx.x % FC, jl = threadIdx.x / FC;
-    const int c = blockIdx.x * FC + cl;
+    const int cl = threadIdx.x % BNF_FC, jl = threadIdx.x / BNF_FC;
+    const int c = blockIdx.x * BNF_FC + cl;
     const int j0 = blockIdx.y * per;
     const int n = gy - j0 < per ? gy - j0 : per;
     double s, ss;
-    reduce_partials(partial + (long)j0 * 2 * C, n, C, c, jl, s, ss);
-    reduce_row_lanes(s, ss);
+    bnf_reduce_partials<false>(partial + (long)j0 * 2 * C, n, C, c, jl, s, ss);
+    bnf_reduce_row_lanes(s, ss);
     if (jl != 0 || c >= C) return;
     out[(long)blockIdx.y * 2 * C + c] = s;
     out[(long)blockIdx.y * 2 * C + C + c] = ss;
@@ -179,25 +108,13 @@ __global__ __launch_bounds__(FINAL_NT) void bn_stats_final_kernel(const double* 
                                                              float* __restrict__ save_invstd,
                                                              float* __restrict__ run_mean,
                                                              float* __restrict__ run_stdinv) {
-    const int cl = threadIdx.x % FC, jl = threadIdx.x / FC;
-    const int c = blockIdx.x * FC + cl;
+    const int cl = threadIdx.x % BNF_FC, jl = threadIdx.x / BNF_FC;
+    const int c = blockIdx.x * BNF_FC + cl;
     double s, ss;
-    reduce_partials(partial, gy, C, c, jl, s, ss);
-    reduce_row_lanes(s, ss);
+    bnf_reduce_partials<false>(partial, gy, C, c, jl, s, ss);
+    bnf_reduce_row_lanes(s, ss);
     if (jl != 0 || c >= C) return;
-    const double mean = s / (double)M;
-    double var = ss / (double)M - mean * mean;  // biased variance (cuDNN)
-    if (var < 0) var = 0;
-    const float fmean = (float)mean;
-    const float finv = (float)(1.0 / sqrt(var + (double)eps));
-    save_mean[c] = fmean;
-    save_invstd[c] = finv;
-    if (run_mean) {
-        // batch_norm.py:75-76: mean <- m*mean + (1-m)*batch_mean ; stdinv <- m*stdinv + (1-m)*batch_invstd
-        const float om = (float)(1.0 - (double)momentum);
-        run_mean[c] = momentum * run_mean[c] + om * fmean;
-        run_stdinv[c] = momentum * run_stdinv[c] + om * finv;
-    }
+    bnf_finish_stats(s, ss, M, eps, momentum, c, save_mean, save_invstd, run_mean, run_stdinv);
 }
 
 // y = relu?( gamma*(x-mean)*invstd + beta (+ res) )
@@ -331,43 +248,20 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
             ss[k] += (double)g[k] * (double)xh;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        red[tid * 8 + k] = s[k];
-        red[tid * 8 + 4 + k] = ss[k];
-    }
-    __syncthreads();
-    if (rsub == 0) {
-        for (int j = 1; j < RS; ++j) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                s[k] += red[(j * LC + cl) * 8 + k];
-                ss[k] += red[(j * LC + cl) * 8 + 4 + k];
-            }
-        }
-        double* p = partial + (long)blockIdx.y * 2 * C;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            p[c + k] = s[k];
-            p[C + c + k] = ss[k];
-        }
-    }
+    bn_reduce_workgroup_tail(s, ss, red, LC, C, c, partial);
 }
 
 // dbeta = sum g ; dgamma = sum g*xhat ; coef[0][c] = dbeta/M ; coef[1][c] = dgamma/M
 __global__ __launch_bounds__(FINAL_NT) void bn_bwd_final_kernel(const double* __restrict__ partial, int gy, long M, int C,
                                                            float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            float* __restrict__ coef) {
-    const int cl = threadIdx.x % FC, jl = threadIdx.x / FC;
-    const int c = blockIdx.x * FC + cl;
+    const int cl = threadIdx.x % BNF_FC, jl = threadIdx.x / BNF_FC;
+    const int c = blockIdx.x * BNF_FC + cl;
     double s, ss;
-    reduce_partials(partial, gy, C, c, jl, s, ss);
-    reduce_row_lanes(s, ss);
+    bnf_reduce_partials<false>(partial, gy, C, c, jl, s, ss);
+    bnf_reduce_row_lanes(s, ss);
     if (jl != 0 || c >= C) return;
-    dbeta[c] = (float)s;
-    dgamma[c] = (float)ss;
-    coef[c] = (float)(s / (double)M);
-    coef[C + c] = (float)(ss / (double)M);
+    bnf_finish_sums(s, ss, M, C, c, dgamma, dbeta, coef);
 }
 
 // dx = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)) ; optional dres = g
@@ -528,9 +422,24 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(const float* __restrict__ 
     }
 }
 
+// the launches more than one entry point makes
+static void launch_stats_partial(const float* x, long M, int C, const BnReduceMap& m, double* partial, hipStream_t stream) {
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, M, C, m.LC, partial);
+}
+static void launch_stats_final(const double* partial, int rows, long M, int C, float eps, float momentum, float* save_mean,
+                               float* save_invstd, float* run_mean, float* run_stdinv, hipStream_t stream) {
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + BNF_FC - 1) / BNF_FC), dim3(FINAL_NT), 0, stream, partial, rows, M, C, eps,
+                       momentum, save_mean, save_invstd, run_mean, run_stdinv);
+}
+static void launch_bwd_final(const double* partial, int rows, long M, int C, float* dgamma, float* dbeta, float* coef,
+                             hipStream_t stream) {
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + BNF_FC - 1) / BNF_FC), dim3(FINAL_NT), 0, stream, partial, rows, M, C, dgamma,
+                       dbeta, coef);
+}
+
 extern "C" size_t denet_bn_workspace_bytes(long M, int C) {
     if (C <= 0 || C % 4) return 0;
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     // partials (at least the 64 rows of a folded list) + 2*C floats of coefficients (backward) / test-mode coefficients
     return (size_t)(m.gy > 64 ? m.gy : 64) * 2 * C * sizeof(double) + (size_t)2 * C * sizeof(float);
 }
@@ -541,11 +450,10 @@ extern "C" int denet_bn_fwd_train(const float* x, const float* res, float* y, co
                                   hipStream_t stream) {
     DENET_CHECK_ARG(x && y && gamma && beta && save_mean && save_invstd && workspace, "bn_fwd_train: null pointer");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_fwd_train: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     double* partial = (double*)workspace;
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, M, C, m.LC, partial);
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, m.gy, M, C, eps,
-                       momentum, save_mean, save_invstd, run_mean, run_stdinv);
+    launch_stats_partial(x, M, C, m, partial, stream);
+    launch_stats_final(partial, m.gy, M, C, eps, momentum, save_mean, save_invstd, run_mean, run_stdinv, stream);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, res, y, gamma, beta, save_mean,
                        save_invstd, M, C, m.LC, relu);
     DENET_CHECK_LAUNCH("bn_fwd_train");
@@ -560,9 +468,8 @@ extern "C" int denet_bn_fwd_train_pre(const float* x, const float* res, float* y
                                       hipStream_t stream) {
     DENET_CHECK_ARG(x && y && gamma && beta && save_mean && save_invstd && partial && rows > 0, "bn_fwd_train_pre: bad arguments");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_fwd_train_pre: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, rows, M, C, eps,
-                       momentum, save_mean, save_invstd, run_mean, run_stdinv);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
+    launch_stats_final(partial, rows, M, C, eps, momentum, save_mean, save_invstd, run_mean, run_stdinv, stream);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, res, y, gamma, beta, save_mean,
                        save_invstd, M, C, m.LC, relu);
     DENET_CHECK_LAUNCH("bn_fwd_train_pre");
@@ -574,8 +481,8 @@ extern "C" int denet_bn_fwd_train_pre(const float* x, const float* res, float* y
 extern "C" int denet_bn_stats_partial(const float* x, void* workspace, int* rows, long M, int C, hipStream_t stream) {
     DENET_CHECK_ARG(x && workspace && rows, "bn_stats_partial: null pointer");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_stats_partial: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, M, C, m.LC, (double*)workspace);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
+    launch_stats_partial(x, M, C, m, (double*)workspace, stream);
     DENET_CHECK_LAUNCH("bn_stats_partial");
     *rows = m.gy;
     return DENET_OK;
@@ -584,8 +491,7 @@ extern "C" int denet_bn_stats_partial(const float* x, void* workspace, int* rows
 extern "C" int denet_bn_stats_final(const double* partial, int rows, long M, int C, float momentum, float eps, float* run_mean,
                                     float* run_stdinv, float* save_mean, float* save_invstd, hipStream_t stream) {
     DENET_CHECK_ARG(partial && rows > 0 && save_mean && save_invstd && M > 0 && C > 0, "bn_stats_final: bad arguments");
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, rows, M, C, eps,
-                       momentum, save_mean, save_invstd, run_mean, run_stdinv);
+    launch_stats_final(partial, rows, M, C, eps, momentum, save_mean, save_invstd, run_mean, run_stdinv, stream);
     DENET_CHECK_LAUNCH("bn_stats_final");
     return DENET_OK;
 }
@@ -594,7 +500,7 @@ extern "C" int denet_bn_apply(const float* x, const float* res, float* y, const 
                               const float* save_mean, const float* save_invstd, long M, int C, int relu, hipStream_t stream) {
     DENET_CHECK_ARG(x && y && gamma && beta && save_mean && save_invstd, "bn_apply: null pointer");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_apply: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, res, y, gamma, beta, save_mean,
                        save_invstd, M, C, m.LC, relu);
     DENET_CHECK_LAUNCH("bn_apply");
@@ -607,12 +513,11 @@ extern "C" int denet_bn_bwd_sums(const float* x, const float* y, const float* dy
     DENET_CHECK_ARG(x && dy && gamma && save_mean && save_invstd && dgamma && dbeta && coef && workspace, "bn_bwd_sums: null pointer");
     DENET_CHECK_ARG(!relu || y || beta, "bn_bwd_sums: the relu mask needs the forward output y, or beta to recompute it");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_bwd_sums: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     double* partial = (double*)workspace;
     hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(m.gx, m.gy), dim3(256), 0, stream, x, y, dy, gamma, beta, save_mean,
                        save_invstd, M, C, m.LC, relu, partial, (const unsigned char*)nullptr, PoolGeom{});
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, m.gy, M, C, dgamma,
-                       dbeta, coef);
+    launch_bwd_final(partial, m.gy, M, C, dgamma, dbeta, coef, stream);
     DENET_CHECK_LAUNCH("bn_bwd_sums");
     return DENET_OK;
 }
@@ -623,7 +528,7 @@ extern "C" int denet_bn_bwd_sums(const float* x, const float* y, const float* dy
 extern "C" int denet_bn_bwd_final(const double* partial, int rows, long M, int C, float* dgamma, float* dbeta, float* coef,
                                   hipStream_t stream) {
     DENET_CHECK_ARG(partial && rows > 0 && dgamma && dbeta && coef && M > 0 && C > 0, "bn_bwd_final: bad arguments");
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, rows, M, C, dgamma, dbeta, coef);
+    launch_bwd_final(partial, rows, M, C, dgamma, dbeta, coef, stream);
     DENET_CHECK_LAUNCH("bn_bwd_final");
     return DENET_OK;
 }
@@ -634,7 +539,7 @@ extern "C" int denet_bn_bwd_apply(const float* x, const float* y, const float* d
     DENET_CHECK_ARG(x && dy && gamma && save_mean && save_invstd && coef && dx, "bn_bwd_apply: null pointer");
     DENET_CHECK_ARG(!relu || y || beta, "bn_bwd_apply: the relu mask needs the forward output y, or beta to recompute it");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_bwd_apply: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(m.gx, m.gy), dim3(256), 0, stream, x, y, dy, gamma, beta, save_mean,
                        save_invstd, coef, dx, dres, M, C, m.LC, relu, (const unsigned char*)nullptr, PoolGeom{});
     DENET_CHECK_LAUNCH("bn_bwd_apply");
@@ -648,7 +553,7 @@ extern "C" int denet_bn_fwd_test(const float* x, const float* res, float* y, con
     // written by an earlier call and the running statistics have not changed since (inference: one kernel per layer)
     DENET_CHECK_ARG(x && y && gamma && beta && run_mean && run_stdinv && coef, "bn_fwd_test: null pointer");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_fwd_test: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     if (!coef_ready)
         hipLaunchKernelGGL(bn_test_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, run_mean, run_stdinv, C, eps,
                            coef, coef + C);
@@ -665,13 +570,12 @@ extern "C" int denet_bn_bwd(const float* x, const float* y, const float* dy, con
                     "bn_bwd: null pointer");
     DENET_CHECK_ARG(!relu || y || beta, "bn_bwd: the relu mask needs the forward output y, or beta to recompute it");
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_bwd: bad shape M=%ld C=%d", M, C);
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     double* partial = (double*)workspace;
     float* coef = (float*)(partial + (size_t)m.gy * 2 * C);
     hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(m.gx, m.gy), dim3(256), 0, stream, x, y, dy, gamma, beta, save_mean,
                        save_invstd, M, C, m.LC, relu, partial, (const unsigned char*)nullptr, PoolGeom{});
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, m.gy, M, C, dgamma,
-                       dbeta, coef);
+    launch_bwd_final(partial, m.gy, M, C, dgamma, dbeta, coef, stream);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(m.gx, m.gy), dim3(256), 0, stream, x, y, dy, gamma, beta, save_mean,
                        save_invstd, coef, dx, dres, M, C, m.LC, relu, (const unsigned char*)nullptr, PoolGeom{});
     DENET_CHECK_LAUNCH("bn_bwd");
@@ -702,10 +606,10 @@ extern "C" int denet_bn_relu_pool_fwd_train_xhat(const float* x, float* y_pool, 
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && k > 0 && k * k <= 255 && stride > 0 && pad >= 0 && pad < k &&
                     (long)N * H * W < (1L << 31), "bn_relu_pool_fwd_train: bad arguments");
     const long M = (long)N * H * W;
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     if (!partial) {
         double* p = (double*)workspace;
-        hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, M, C, m.LC, p);
+        launch_stats_partial(x, M, C, m, p, stream);
         partial = p;
         rows = m.gy;
     } else if (rows > 2048 && workspace) {
@@ -713,12 +617,11 @@ extern "C" int denet_bn_relu_pool_fwd_train_xhat(const float* x, float* y_pool, 
         const int per = (rows + 63) / 64;
         const int slices = (rows + per - 1) / per;
         double* folded = (double*)workspace;
-        hipLaunchKernelGGL(bn_stats_fold_kernel, dim3((C + FC - 1) / FC, slices), dim3(FINAL_NT), 0, stream, partial, rows, per, C, folded);
+        hipLaunchKernelGGL(bn_stats_fold_kernel, dim3((C + BNF_FC - 1) / BNF_FC, slices), dim3(FINAL_NT), 0, stream, partial, rows, per, C, folded);
         partial = folded;
         rows = slices;
     }
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, rows, M, C, eps,
-                       momentum, save_mean, save_invstd, run_mean, run_stdinv);
+    launch_stats_final(partial, rows, M, C, eps, momentum, save_mean, save_invstd, run_mean, run_stdinv, stream);
     const PoolGeom g = pool_geom(H, W, OH, OW, k, stride, pad, C);
     const long total = (long)N * OH * OW * (C / 4);
     long blocks = (total + 255) / 256;
@@ -750,7 +653,7 @@ static void launch_pool_apply(const float* x, const float* dy_pool, const unsign
         return;
     }
     const long M = (long)N * H * W;
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     const PoolGeom g = pool_geom(H, W, OH, OW, k, stride, pad, C);
     hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(m.gx, m.gy), dim3(256), 0, stream, x, (const float*)nullptr, dy_pool,
                        gamma, beta, save_mean, save_invstd, coef, dx, (float*)nullptr, M, C, m.LC, 1, argmax, g);
@@ -766,14 +669,13 @@ extern "C" int denet_bn_relu_pool_bwd(const float* x, const float* dy_pool, cons
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 && k > 0 && stride > 0 && pad >= 0 && (long)N * H * W < (1L << 31),
                     "bn_relu_pool_bwd: bad arguments");
     const long M = (long)N * H * W;
-    BnMap m = bn_map(M, C);
+    BnReduceMap m = bn_map(M, C, BN_WGS);
     double* partial = (double*)workspace;
     float* coef = (float*)(partial + (size_t)m.gy * 2 * C);
     const PoolGeom g = pool_geom(H, W, OH, OW, k, stride, pad, C);
     hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3(m.gx, m.gy), dim3(256), 0, stream, x, (const float*)nullptr, dy_pool,
                        gamma, beta, save_mean, save_invstd, M, C, m.LC, 1, partial, argmax, g);
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, m.gy, M, C, dgamma,
-                       dbeta, coef);
+    launch_bwd_final(partial, m.gy, M, C, dgamma, dbeta, coef, stream);
     launch_pool_apply(x, dy_pool, argmax, gamma, beta, save_mean, save_invstd, coef, dx, N, H, W, C, OH, OW, k, stride, pad, stream);
     DENET_CHECK_LAUNCH("bn_relu_pool_bwd");
     return DENET_OK;
@@ -793,12 +695,11 @@ extern "C" int denet_bn_relu_pool_bwd_sums(const float* xhat_pool, const float* 
                     "bn_relu_pool_bwd_sums: null pointer");
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 4 == 0, "bn_relu_pool_bwd_sums: bad arguments");
     const long Mp = (long)N * OH * OW;
-    BnMap m = bn_map(Mp, C);
+    BnReduceMap m = bn_map(Mp, C, BN_WGS);
     double* partial = (double*)workspace;
     hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(m.gx, m.gy), dim3(256), 0, stream, xhat_pool, y_pool, dy_pool, ones,
                        (const float*)nullptr, zeros, ones, Mp, C, m.LC, 1, partial, (const unsigned char*)nullptr, PoolGeom{});
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FC - 1) / FC), dim3(FINAL_NT), 0, stream, partial, m.gy, (long)N * H * W, C,
-                       dgamma, dbeta, coef);
+    launch_bwd_final(partial, m.gy, (long)N * H * W, C, dgamma, dbeta, coef, stream);
     DENET_CHECK_LAUNCH("bn_relu_pool_bwd_sums");
     return DENET_OK;
 }

@@ -11,14 +11,15 @@
 //     fetch_add on the group's counter (cdna_hip_programming.md, Guideline 16 / the split-K seam recipe in its sc1 form: no
 //     release fence, hence no write-back of the XCD's whole L2 per workgroup);
 //   * the workgroup that draws the last ticket reads ALL rows of its columns with sc1 loads (past its own L1 / the XCD's L2) in the
-//     order of the separate kernels - one wave per FC channels, 64 / FC row lanes striding over the rows with four loads in
-//     flight, a shuffle tree - so the result is BIT-IDENTICAL to what bn_stats_final_kernel / bn_bwd_final_kernel compute from
-//     the same rows (tests compare the two forms exactly: a stale row would show as a different bit);
+//     order of the separate kernels - bn_reduce.h, the one text of that order, which both sides call: one wave per BNF_FC
+//     channels, BNF_FJ row lanes striding over the rows with four loads in flight, a shuffle tree - so the result is
+//     BIT-IDENTICAL to what bn_stats_final_kernel / bn_bwd_final_kernel compute from the same rows (tests compare the two forms
+//     exactly: a stale row would show as a different bit);
 //   * it leaves the counter at zero again: the buffers are at rest between launches (allocated zeroed by the host).
 // Which batch norm the sums belong to arrives through an "armed" descriptor (denet_bn_final_arm, include/denet_hip.h): the
 // C-ABI of the producing passes is unchanged.
 #pragma once
-#include "common.h"
+#include "bn_reduce.h"
 
 struct BnFinalDev {
     unsigned* counter;      // [column groups], zero at rest; null: the rows are reduced by a later launch
@@ -36,145 +37,11 @@ struct BnFinalDev {
 // descriptor (counter == null) unless one is armed for this kind, channel count and at most the armed number of column groups
 BnFinalDev denet_bn_final_take(int kind, int C, int groups);
 
-constexpr int BNF_FC = 2, BNF_FJ = 64 / BNF_FC;      // channels per wave, row lanes (bn.hip: FC, FJ)
-
-typedef __attribute__((address_space(1))) unsigned long long bnf_gu64;
 typedef __attribute__((address_space(1))) unsigned bnf_gu32;
 
-// a partial sum: write-through (sc1) 8-byte store / load past L1 and the XCD's L2
+// a partial sum: write-through (sc1) 8-byte store (read back past L1 and the XCD's L2 by bnf_load<true>, bn_reduce.h)
 __device__ __forceinline__ void bnf_store(double* p, double v) {
     __hip_atomic_store((bnf_gu64*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool SC1>
-__device__ __forceinline__ double bnf_load(const double* p) {
-    if (SC1) return __longlong_as_double((long long)__hip_atomic_load((const bnf_gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    return *p;
-}
-
-__device__ __forceinline__ void bnf_reduce_row_lanes(double& s, double& ss) {
-#pragma unroll
-    for (int off = BNF_FC; off < 64; off <<= 1) {
-        s += __shfl_xor(s, off, 64);
-        ss += __shfl_xor(ss, off, 64);
-    }
-}
-
-// lane (c, jl) of a wave: the sums over rows jl, jl + FJ, ... of column c (4 independent row loads in flight)
-template <bool SC1>
-__device__ __forceinline__ void bnf_reduce_partials(const double* __restrict__ partial, int gy, int C, int c, int jl, double& s,
-                                                    double& ss) {
-    s = 0;
-    ss = 0;
-    if (c < C) {
-        int j = jl;
-        for (; j + 3 * BNF_FJ < gy; j += 4 * BNF_FJ) {
-            const double a0 = bnf_load<SC1>(partial + (long)j * 2 * C + c), b0 = bnf_load<SC1>(partial + (long)j * 2 * C + C + c);
-            const double a1 = bnf_load<SC1>(partial + (long)(j + BNF_FJ) * 2 * C + c),
-                         b1 = bnf_load<SC1>(partial + (long)(j + BNF_FJ) * 2 * C + C + c);
-            const double a2 = bnf_load<SC1>(partial + (long)(j + 2 * BNF_FJ) * 2 * C + c),
-                         b2 = bnf_load<SC1>(partial + (long)(j + 2 * BNF_FJ) * 2 * C + C + c);
-            const double a3 = bnf_load<SC1>(partial + (long)(j + 3 * BNF_FJ) * 2 * C + c),
-                         b3 = bnf_load<SC1>(partial + (long)(j + 3 * BNF_FJ) * 2 * C + C + c);
-            s += (a0 + a1) + (a2 + a3);
-            ss += (b0 + b1) + (b2 + b3);
-        }
-        for (; j < gy; j += BNF_FJ) {
-            s += bnf_load<SC1>(partial + (long)j * 2 * C + c);
-            ss += bnf_load<SC1>(partial + (long)j * 2 * C + C + c);
-        }
-    }
-}
-
-// the same sums for U columns c[0..U-1] of one lane at once: the loads of all U columns of a round are issued together (a wave
-// that walks its column pairs one after the other is latency-bound: two dependent round trips per pair), the additions of every
-// column are those of bnf_reduce_partials in the same order
-template <bool SC1, int U>
-__device__ __forceinline__ void bnf_reduce_partials_multi(const double* __restrict__ partial, int gy, int C, const int (&c)[U], int jl,
-                                                          double (&s)[U], double (&ss)[U]) {
-    int cs[U];          // (a column outside the tensor: a valid address is loaded - no exec-masked load, which would end the
-                        // scheduling region and drain the loads in flight - and the caller drops the result)
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        s[u] = ss[u] = 0;
-        cs[u] = c[u] < C ? c[u] : 0;
-    }
-    int j = jl;
-    // two groups of four rows per lane at a time (the loads of 2 x 4 x 2 x U values leave together: 256 rows - what a fused
-    // kernel's launch leaves - are ONE round trip for the last workgroup, on whose latency the end of the launch waits)
-    for (; j + 7 * BNF_FJ < gy; j += 8 * BNF_FJ) {
-        double a[U][8], b[U][8];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const double* row = partial + (long)(j + r * BNF_FJ) * 2 * C;
-                a[u][r] = bnf_load<SC1>(row + cs[u]);
-                b[u][r] = bnf_load<SC1>(row + C + cs[u]);
-            }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            s[u] += (a[u][0] + a[u][1]) + (a[u][2] + a[u][3]);
-            ss[u] += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
-            s[u] += (a[u][4] + a[u][5]) + (a[u][6] + a[u][7]);
-            ss[u] += (b[u][4] + b[u][5]) + (b[u][6] + b[u][7]);
-        }
-    }
-    for (; j + 3 * BNF_FJ < gy; j += 4 * BNF_FJ) {
-        double a[U][4], b[U][4];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const double* row = partial + (long)(j + r * BNF_FJ) * 2 * C;
-                a[u][r] = bnf_load<SC1>(row + cs[u]);
-                b[u][r] = bnf_load<SC1>(row + C + cs[u]);
-            }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            s[u] += (a[u][0] + a[u][1]) + (a[u][2] + a[u][3]);
-            ss[u] += (b[u][0] + b[u][1]) + (b[u][2] + b[u][3]);
-        }
-    }
-    for (; j < gy; j += BNF_FJ) {
-        double a[U], b[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const double* row = partial + (long)j * 2 * C;
-            a[u] = bnf_load<SC1>(row + cs[u]);
-            b[u] = bnf_load<SC1>(row + C + cs[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            s[u] += a[u];
-            ss[u] += b[u];
-        }
-    }
-}
-
-// what the lane with jl == 0 does with the sums of channel c (the bodies of bn_stats_final_kernel / bn_bwd_final_kernel)
-__device__ __forceinline__ void bnf_finish_stats(double s, double ss, long M, float eps, float momentum, int c,
-                                                 float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                 float* __restrict__ run_mean, float* __restrict__ run_stdinv) {
-    const double mean = s / (double)M;
-    double var = ss / (double)M - mean * mean;  // biased variance (cuDNN)
-    if (var < 0) var = 0;
-    const float fmean = (float)mean;
-    const float finv = (float)(1.0 / sqrt(var + (double)eps));
-    save_mean[c] = fmean;
-    save_invstd[c] = finv;
-    if (run_mean) {
-        // batch_norm.py:75-76: mean <- m*mean + (1-m)*batch_mean ; stdinv <- m*stdinv + (1-m)*batch_invstd
-        const float om = (float)(1.0 - (double)momentum);
-        run_mean[c] = momentum * run_mean[c] + om * fmean;
-        run_stdinv[c] = momentum * run_stdinv[c] + om * finv;
-    }
-}
-__device__ __forceinline__ void bnf_finish_sums(double s, double ss, long M, int C, int c, float* __restrict__ dgamma,
-                                                float* __restrict__ dbeta, float* __restrict__ coef) {
-    dbeta[c] = (float)s;
-    dgamma[c] = (float)ss;
-    coef[c] = (float)(s / (double)M);
-    coef[C + c] = (float)(ss / (double)M);
 }
 
 // Called by EVERY thread of a workgroup of NT threads (a multiple of 64) right after its threads have written the workgroup's

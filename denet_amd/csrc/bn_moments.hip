@@ -7,37 +7,17 @@
 //      through LDS and writes one row of the slab partial[gy][2][C]. The shift (the "shifted data" form of the textbook
 //      variance algorithms) keeps sum(d*d)/M - (sum(d)/M)^2 free of cancellation when |mean| >> std, which E[x^2] - mean^2 is not:
 //      the relative error is eps * (1 + (mean - x0)^2 / var), x0 being one sample of the channel.
-//   2. fold: one wave per two channels reduces the slab rows in a fixed order and adds the batch's moments into acc.
+//   2. fold: one wave per two channels reduces the slab rows in a fixed order (bn_reduce.h: the order of every two-stage
+//      batch-norm reduction) and adds the batch's moments into acc.
 //   No atomics: the result is bitwise the same from run to run. No allocation and no host synchronisation.
 // finish: acc, n -> run_mean = f32(acc0 / n), run_stdinv = 1 / sqrt(f32(acc1 / n) + 1e-5) in float32 with correctly rounded
 // add, square root and division (update_bn.py:63-66 evaluated by numpy in float32).
-#include "common.h"
+#include "bn_reduce.h"
 #include "../../include/denet_hip.h"
 
 namespace {
 
-struct MomMap {
-    int LC;      // lanes along channels (float4 units)
-    int RS;      // rows handled concurrently by one workgroup
-    int gx, gy;  // grid
-};
-
-MomMap mom_map(long M, int C) {
-    MomMap m;
-    const int c4 = C / 4;
-    int lc = 1;
-    while (lc < 256 && (c4 % (lc * 2)) == 0) lc *= 2;
-    m.LC = lc;
-    m.RS = 256 / lc;
-    m.gx = c4 / lc;
-    const long rows_blocks = (M + m.RS - 1) / m.RS;
-    // a memory-bound pass: about 2048 workgroups (8 per CU), grid-stride over the rest
-    int gy = 2048 / m.gx;
-    if (gy < 1) gy = 1;
-    if (gy > rows_blocks) gy = (int)rows_blocks;
-    m.gy = gy;
-    return m;
-}
+constexpr int MOM_WGS = 2048;   // bn_map's target: a memory-bound pass, about 8 workgroups per CU, grid-stride over the rest
 
 // partial[gy][2][C] : sum(x - x0), sum((x - x0)^2), x0 = x[row 0]
 __global__ __launch_bounds__(256) void bn_moments_partial_kernel(const float* __restrict__ x, long M, int C, int LC,
@@ -74,57 +54,19 @@ __global__ __launch_bounds__(256) void bn_moments_partial_kernel(const float* __
             ss[k] += d * d;
         }
     }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        red[tid * 8 + k] = s[k];
-        red[tid * 8 + 4 + k] = ss[k];
-    }
-    __syncthreads();
-    if (rsub == 0) {
-        for (int j = 1; j < RS; ++j) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                s[k] += red[(j * LC + cl) * 8 + k];
-                ss[k] += red[(j * LC + cl) * 8 + 4 + k];
-            }
-        }
-        double* p = partial + (long)blockIdx.y * 2 * C;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            p[c + k] = s[k];
-            p[C + c + k] = ss[k];
-        }
-    }
+    bn_reduce_workgroup_tail(s, ss, red, LC, C, c, partial);
 }
 
-// one wave per MC channels: MJ = 64 / MC lanes stride over the slab rows (four loads in flight each), a shuffle tree adds them
-constexpr int MC = 2, MJ = 64 / MC, MOM_NT = 64;
+// one wave per BNF_FC channels: BNF_FJ lanes stride over the slab rows (four loads in flight each), a shuffle tree adds them
+constexpr int MOM_NT = 64;
 
 __global__ __launch_bounds__(MOM_NT) void bn_moments_fold_kernel(const float* __restrict__ x, const double* __restrict__ partial,
                                                                  int gy, long M, int C, double* __restrict__ acc) {
-    const int cl = threadIdx.x % MC, jl = threadIdx.x / MC;
-    const int c = blockIdx.x * MC + cl;
-    double s = 0, ss = 0;
-    if (c < C) {
-        int j = jl;
-        for (; j + 3 * MJ < gy; j += 4 * MJ) {
-            const double a0 = partial[(long)j * 2 * C + c], b0 = partial[(long)j * 2 * C + C + c];
-            const double a1 = partial[(long)(j + MJ) * 2 * C + c], b1 = partial[(long)(j + MJ) * 2 * C + C + c];
-            const double a2 = partial[(long)(j + 2 * MJ) * 2 * C + c], b2 = partial[(long)(j + 2 * MJ) * 2 * C + C + c];
-            const double a3 = partial[(long)(j + 3 * MJ) * 2 * C + c], b3 = partial[(long)(j + 3 * MJ) * 2 * C + C + c];
-            s += (a0 + a1) + (a2 + a3);
-            ss += (b0 + b1) + (b2 + b3);
-        }
-        for (; j < gy; j += MJ) {
-            s += partial[(long)j * 2 * C + c];
-            ss += partial[(long)j * 2 * C + C + c];
-        }
-    }
-#pragma unroll
-    for (int off = MC; off < 64; off <<= 1) {
-        s += __shfl_xor(s, off, 64);
-        ss += __shfl_xor(ss, off, 64);
-    }
+    const int cl = threadIdx.x % BNF_FC, jl = threadIdx.x / BNF_FC;
+    const int c = blockIdx.x * BNF_FC + cl;
+    double s, ss;
+    bnf_reduce_partials<false>(partial, gy, C, c, jl, s, ss);
+    bnf_reduce_row_lanes(s, ss);
     if (jl != 0 || c >= C) return;
     const double md = s / (double)M;
     double var = ss / (double)M - md * md;   // biased variance of the shifted values = of x
@@ -151,7 +93,7 @@ __global__ __launch_bounds__(256) void bn_moments_finish_kernel(const double* __
 
 extern "C" size_t denet_bn_moments_workspace_bytes(long M, int C) {
     if (M <= 0 || C <= 0 || C % 4) return 0;
-    const MomMap m = mom_map(M, C);
+    const BnReduceMap m = bn_map(M, C, MOM_WGS);
     return (size_t)m.gy * 2 * C * sizeof(double);
 }
 
@@ -161,10 +103,10 @@ extern "C" int denet_bn_moments_accumulate(const float* x, double* acc, void* wo
     DENET_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0, "bn_moments_accumulate: bad shape M=%ld C=%d", M, C);
     DENET_CHECK_ARG(workspace_bytes >= denet_bn_moments_workspace_bytes(M, C), "bn_moments_accumulate: workspace of %zu bytes < %zu",
                     workspace_bytes, denet_bn_moments_workspace_bytes(M, C));
-    const MomMap m = mom_map(M, C);
+    const BnReduceMap m = bn_map(M, C, MOM_WGS);
     double* partial = (double*)workspace;
     hipLaunchKernelGGL(bn_moments_partial_kernel, dim3(m.gx, m.gy), dim3(256), 0, stream, x, M, C, m.LC, partial);
-    hipLaunchKernelGGL(bn_moments_fold_kernel, dim3((C + MC - 1) / MC), dim3(MOM_NT), 0, stream, x, (const double*)partial, m.gy, M,
+    hipLaunchKernelGGL(bn_moments_fold_kernel, dim3((C + BNF_FC - 1) / BNF_FC), dim3(MOM_NT), 0, stream, x, (const double*)partial, m.gy, M,
                        C, acc);
     DENET_CHECK_LAUNCH("bn_moments_accumulate");
     return DENET_OK;

@@ -26,7 +26,7 @@
 //   bn_renorm_grad_fold_kernel     s1, s2 (denet_bn_bwd_sums, written to scratch) -> dgamma = r * s2 + d * s1, dbeta = s1 in the
 //                                  gradient slab; the slab never holds s2
 // state [4][C] floats: r | d | gamma_eff | beta_eff, written by the forward call, read by the backward call of the same step.
-#include "bn_final.h"
+#include "bn_reduce.h"
 #include "../../include/denet_hip.h"
 #include <math.h>
 

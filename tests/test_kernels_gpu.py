@@ -934,6 +934,61 @@ def test_bn_fwd_bwd(hip, shape, relu, res):
         _close(dres, r.grad)
 
 
+def _bn_final_order(p):
+    """csrc/bn_reduce.h in numpy float64: the sum of the rows p [rows] of one column as the second stage adds them - lane jl of
+    32 takes rows jl, jl + 32, ...: four at a time as (p[j] + p[j+32]) + (p[j+64] + p[j+96]) while j + 96 < rows, then one by
+    one; the lane sums go through a butterfly over the xor offsets 1, 2, 4, 8, 16; lane 0 holds the result"""
+    rows = len(p)
+    lanes = np.zeros(32, np.float64)
+    for jl in range(32):
+        acc, j = np.float64(0), jl
+        while j + 96 < rows:
+            acc = acc + ((p[j] + p[j + 32]) + (p[j + 64] + p[j + 96]))
+            j += 128
+        while j < rows:
+            acc = acc + p[j]
+            j += 32
+        lanes[jl] = acc
+    for off in (1, 2, 4, 8, 16):
+        lanes = lanes + lanes[np.arange(32) ^ off]
+    return lanes[0]
+
+
+@pytest.mark.parametrize("rows", [1, 2, 32, 33, 96, 97, 128, 129, 300])
+def test_bn_final_summation_order_is_pinned(hip, rows):
+    """the second stage of the batch-norm reductions (denet_bn_bwd_final over a given partial [rows][2][C]) is DEFINED bit for
+    bit: the order of csrc/bn_reduce.h, emulated in numpy float64 (_bn_final_order). 33 rows: the first count that gives a lane
+    two rows; 97: the first that enters the four-loads-in-flight loop. The rows cancel (a half, its negation permuted per column,
+    magnitudes up to 2^40), so what is left of a sum is the rounding of ITS order: a plain in-order sum gives other float32
+    values, which the test checks on the host before it trusts the comparison"""
+    from denet_amd import ops
+    C, M = 6, 3
+    rng = np.random.RandomState(rows)
+    h = rows // 2
+    a = rng.standard_normal((h, 2, C)) * 2.0 ** rng.randint(0, 40, (h, 2, C))
+    b = np.empty_like(a)
+    for k in range(2):
+        for c in range(C):
+            b[:, k, c] = -a[rng.permutation(h), k, c]
+    p = np.concatenate([a, b] + ([rng.standard_normal((1, 2, C))] if rows % 2 else []))
+    assert p.shape == (rows, 2, C)
+    want = np.array([[_bn_final_order(p[:, k, c]) for c in range(C)] for k in range(2)])
+    if rows >= 32:
+        plain = np.zeros((2, C))
+        for j in range(rows):
+            plain = plain + p[j]
+        differ = int((plain.astype(np.float32) != want.astype(np.float32)).sum())
+        assert differ >= 6, "the inputs do not show the order: an in-order sum differs in %d of 12 values" % differ
+    partial = torch.from_numpy(p).cuda()
+    dgamma, dbeta, coef = ops.empty(C), ops.empty(C), ops.empty(2 * C)
+    ops.check(ops._L().denet_bn_bwd_final(ops.ptr(partial), rows, M, C, ops.ptr(dgamma), ops.ptr(dbeta), ops.ptr(coef),
+                                          ops.stream_ptr()), "bn_bwd_final")
+    bits = lambda t: t.cpu().numpy().view(np.uint32)
+    assert np.array_equal(bits(dbeta), want[0].astype(np.float32).view(np.uint32))
+    assert np.array_equal(bits(dgamma), want[1].astype(np.float32).view(np.uint32))
+    assert np.array_equal(bits(coef), (want / np.float64(M)).astype(np.float32).reshape(2 * C).view(np.uint32))
+
+
 def test_bn_known_answer(hip):
     """Reference's own KAT (denet/layer/batch_norm.py:131-154): x~U(0,1) (64,128,32,32), running stdinv mean
     = 0.9 + 0.1/sqrt(1/12 + 1e-5) = 1.24641, running mean = 0.1*mean(x), output mean 0 / std 1."""
