@@ -7,8 +7,10 @@
 // rows; LC = gcd(C/4, 256) lanes cover consecutive channels so a wave reads >= 256 contiguous bytes.
 // Per-channel reductions are accumulated in fp64 per thread, combined through LDS, written as
 // per-workgroup partials and finished by a second tiny kernel: deterministic, no atomics. The order of both stages is
-// bn_reduce.h's, shared with every other reader and writer of such partials.
+// bn_reduce.h's, shared with every other reader and writer of such partials; the pointwise expressions are bn_pointwise.h's,
+// shared with the Winograd transforms that evaluate a batch norm on the fly (winograd.hip).
 #include "bn_reduce.h"
+#include "bn_pointwise.h"
 #include "../../include/denet_hip.h"
 #include <stdlib.h>
 
@@ -126,23 +128,13 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     const int tid = threadIdx.x;
     const int cl = tid % LC, rsub = tid / LC, RS = 256 / LC;
     const int c = (blockIdx.x * LC + cl) * 4;
-    float sc[4], sh[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sc[k] = gamma[c + k] * invstd[c + k];
-        sh[k] = beta[c + k] - mean[c + k] * sc[k];
-    }
+    BnQuad bq;
+    bn_quad_load(bq, gamma, beta, mean, invstd, c);
     for (long r = (long)blockIdx.y * RS + rsub; r < M; r += (long)gridDim.y * RS) {
         const long o = r * C + c;
-        f32x4 v = *(const f32x4*)(x + o);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = fmaf(v[k], sc[k], sh[k]);
-        if (res) v += *(const f32x4*)(res + o);
-        if (relu) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
-        }
-        *(f32x4*)(y + o) = v;
+        f32x4 rv = {0.f, 0.f, 0.f, 0.f};
+        if (res) rv = *(const f32x4*)(res + o);
+        *(f32x4*)(y + o) = bn_forward(bq, *(const f32x4*)(x + o), res != nullptr, rv, relu);
     }
 }
 
@@ -164,12 +156,9 @@ __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const float* __restr
         const int ox = (int)(q - t * (uint32_t)g.OW);
         const int n = (int)g.foh.div(t);
         const int oy = (int)(t - (uint32_t)n * (uint32_t)g.OH);
-        float sc[4], sh[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            sc[e] = gamma[c + e] * invstd[c + e];
-            sh[e] = beta[c + e] - mean[c + e] * sc[e];
-        }
+        BnQuad bq;
+        bn_quad_load(bq, gamma, beta, mean, invstd, c);
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         f32x4 best = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, bx = {0.f, 0.f, 0.f, 0.f};
         int bi[4] = {0, 0, 0, 0};
         for (int ky = 0; ky < g.k; ++ky) {
@@ -179,11 +168,11 @@ __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const float* __restr
                 const int ix = ox * g.s - g.pad + kx;
                 if ((unsigned)ix >= (unsigned)g.W) continue;
                 const f32x4 v = *(const f32x4*)(x + (((long)n * g.H + iy) * g.W + ix) * C + c);
+                const f32x4 yv = bn_forward(bq, v, false, z, 1);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float yv = fmaxf(fmaf(v[e], sc[e], sh[e]), 0.f);
-                    if (yv > best[e]) {
-                        best[e] = yv;
+                    if (yv[e] > best[e]) {
+                        best[e] = yv[e];
                         bx[e] = v[e];
                         bi[e] = ky * g.k + kx;
                     }
@@ -192,12 +181,7 @@ __global__ __launch_bounds__(256) void bn_apply_pool_kernel(const float* __restr
         }
         *(f32x4*)(yp + i * 4) = best;
         *(uchar4*)(arg + i * 4) = make_uchar4((unsigned char)bi[0], (unsigned char)bi[1], (unsigned char)bi[2], (unsigned char)bi[3]);
-        if (xh) {
-            f32x4 h;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) h[e] = (bx[e] - mean[c + e]) * invstd[c + e];     // bn_bwd_partial_kernel's expression
-            *(f32x4*)(xh + i * 4) = h;
-        }
+        if (xh) *(f32x4*)(xh + i * 4) = bn_xhat(bq, bx);
     }
 }
 
@@ -218,34 +202,19 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float* __rest
     const int tid = threadIdx.x;
     const int cl = tid % LC, rsub = tid / LC, RS = 256 / LC;
     const int c = (blockIdx.x * LC + cl) * 4;
-    float mu[4], is[4], sc[4], sh[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mu[k] = mean[c + k];
-        is[k] = invstd[c + k];
-        sc[k] = gamma[c + k] * is[k];
-        sh[k] = (beta ? beta[c + k] : 0.f) - mu[k] * sc[k];
-    }
+    BnQuad bq;
+    bn_quad_load<false, true>(bq, gamma, beta, mean, invstd, c);
     double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
     for (long r = (long)blockIdx.y * RS + rsub; r < M; r += (long)gridDim.y * RS) {
         const long o = r * C + c;
         const f32x4 xv = *(const f32x4*)(x + o);
         f32x4 g = POOL ? pool_gather(dy, arg, pg, r, C, c) : *(const f32x4*)(dy + o);
-        if (relu) {
-            if (y) {
-                const f32x4 yv = *(const f32x4*)(y + o);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = fmaf(xv[k], sc[k], sh[k]) > 0.f ? g[k] : 0.f;
-            }
-        }
+        if (relu) g = y ? bn_mask_y(g, *(const f32x4*)(y + o)) : bn_mask_x(bq, g, xv);
+        const f32x4 xh = bn_xhat(bq, xv);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float xh = (xv[k] - mu[k]) * is[k];
             s[k] += (double)g[k];
-            ss[k] += (double)g[k] * (double)xh;
+            ss[k] += (double)g[k] * (double)xh[k];
         }
     }
     bn_reduce_workgroup_tail(s, ss, red, LC, C, c, partial);
@@ -278,37 +247,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     const int tid = threadIdx.x;
     const int cl = tid % LC, rsub = tid / LC, RS = 256 / LC;
     const int c = (blockIdx.x * LC + cl) * 4;
-    float mu[4], is[4], sc[4], sh[4], mg[4], mgx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mu[k] = mean[c + k];
-        is[k] = invstd[c + k];
-        sc[k] = gamma[c + k] * is[k];
-        sh[k] = (beta ? beta[c + k] : 0.f) - mu[k] * sc[k];
-        mg[k] = coef[c + k];
-        mgx[k] = coef[C + c + k];
-    }
+    BnQuad bq;
+    bn_quad_load<false, true>(bq, gamma, beta, mean, invstd, c);
+    bn_quad_load_coef(bq, coef, C, c);
     for (long r = (long)blockIdx.y * RS + rsub; r < M; r += (long)gridDim.y * RS) {
         const long o = r * C + c;
         const f32x4 xv = *(const f32x4*)(x + o);
         f32x4 g = POOL ? pool_gather(dy, arg, pg, r, C, c) : *(const f32x4*)(dy + o);
-        if (relu) {
-            if (y) {
-                const f32x4 yv = *(const f32x4*)(y + o);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = fmaf(xv[k], sc[k], sh[k]) > 0.f ? g[k] : 0.f;
-            }
-        }
-        f32x4 d;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float xh = (xv[k] - mu[k]) * is[k];
-            d[k] = sc[k] * (g[k] - mg[k] - xh * mgx[k]);
-        }
-        *(f32x4*)(dx + o) = d;
+        if (relu) g = y ? bn_mask_y(g, *(const f32x4*)(y + o)) : bn_mask_x(bq, g, xv);
+        *(f32x4*)(dx + o) = bn_backward(bq, g, xv);
         if (dres) *(f32x4*)(dres + o) = g;
     }
 }
@@ -333,16 +280,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_quad_kernel(const float
         const int qx = (int)(q - t * (uint32_t)OW);
         const int n = (int)foh.div(t);
         const int qy = (int)(t - (uint32_t)n * (uint32_t)OH);
-        float mu[4], is[4], sc[4], sh[4], mg[4], mgx[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mu[k] = mean[c + k];
-            is[k] = invstd[c + k];
-            sc[k] = gamma[c + k] * is[k];
-            sh[k] = (beta ? beta[c + k] : 0.f) - mu[k] * sc[k];
-            mg[k] = coef[c + k];
-            mgx[k] = coef[C + c + k];
-        }
+        BnQuad bq;
+        bn_quad_load<false, true>(bq, gamma, beta, mean, invstd, c);
+        bn_quad_load_coef(bq, coef, C, c);
         // the four windows: w[a][b] = window (qy + a, qx + b); outside the pooled map: no window (tap 255 matches nothing)
         f32x4 wv[2][2];
         uchar4 wa[2][2];
@@ -377,15 +317,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_pool_quad_kernel(const float
                     }
                 const long o = (((long)n * H + 2 * qy + py) * W + 2 * qx + px) * C + c;
                 const f32x4 xv = *(const f32x4*)(x + o);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) g[k] = fmaf(xv[k], sc[k], sh[k]) > 0.f ? g[k] : 0.f;
-                f32x4 d;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float xh = (xv[k] - mu[k]) * is[k];
-                    d[k] = sc[k] * (g[k] - mg[k] - xh * mgx[k]);
-                }
-                *(f32x4*)(dx + o) = d;
+                *(f32x4*)(dx + o) = bn_backward(bq, bn_mask_x(bq, g, xv), xv);
             }
     }
 }

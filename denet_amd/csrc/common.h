@@ -33,6 +33,20 @@ void denet_set_error(const char* fmt, ...);
 int denet_prof_begin(int mode, int bm, int bn, int nbuf, hipStream_t stream);
 void denet_prof_end(int idx, hipStream_t stream);
 
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the DEVICE that is current when it is set, so a launcher that sets it
+// once per process leaves every further GPU at the 64 KB default. `done`: the launcher's own static record, one flag per device.
+constexpr int DENET_MAX_DEVICES = 64;
+static inline hipError_t denet_allow_dynamic_lds(const void* kernel, int bytes, bool (&done)[DENET_MAX_DEVICES]) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool known = dev >= 0 && dev < DENET_MAX_DEVICES;
+    if (known && done[dev]) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && known) done[dev] = true;
+    return e;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -16,7 +16,7 @@
 //                 Inside an 8-wide k block lane-half h consumes k = 4h..4h+3 for both operands, so the
 //                 reduction order is a fixed permutation of k (legal: the sum is over the same terms).
 // Launch:         1-D grid over tiles with an XCD-aware remap (8 XCDs, private L2 each).
-#include "common.h"
+#include "wino.h"
 #include "bn_final.h"
 #include "../../include/denet_hip.h"
 #include <map>

@@ -18,7 +18,7 @@
 // what is stored, or the backward sums of the batch norm whose output gradient is written.
 // Association: Y is accumulated component by component instead of A^T (M A) column by column: same sums, other rounding
 // (measured against fp64 in tests/test_conv_fullsize_gpu.py like every other pass).
-#include "common.h"
+#include "wino.h"
 #include "bn_final.h"
 #include "../../include/denet_hip.h"
 #include <stdlib.h>
@@ -69,7 +69,6 @@ struct W4Params {
 };
 
 constexpr int W4_OOB = (int)0xF0000000u;
-constexpr float W4_AT[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 1, 1, 4, 4, 0}, {0, 1, -1, 8, -8, 1}};
 
 // s_waitcnt vmcnt(vm) only (lgkmcnt / expcnt left alone) and the compiler kept from moving memory operations across
 #define W4_WAIT_VM(vm) __builtin_amdgcn_s_waitcnt(((vm) & 15) | ((((vm) >> 4) & 3) << 14) | (7 << 4) | (15 << 8))
@@ -227,7 +226,7 @@ __device__ __forceinline__ void wino4f_body(const W4Params& p) {
             const f32x4 M = Mc[nb][0] + Mc[nb][1];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float c = W4_AT[j][m];
+                const float c = Wino<4>::AT[j][m];
                 // the first contribution to Z[j] of a row: m = 0 for j = 0, m = 1 for the others (AT[j][0] = 0)
                 const bool first = (j == 0) ? m == 0 : m == 1;
                 if (c != 0.f) {
@@ -238,7 +237,7 @@ __device__ __forceinline__ void wino4f_body(const W4Params& p) {
             if (m == 5) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float c = W4_AT[i][l];
+                    const float c = Wino<4>::AT[i][l];
                     // the first contribution to Y[i][.]: row 0 for i = 0, row 1 for the others
                     const bool first = (i == 0) ? l == 0 : l == 1;
                     if (c != 0.f) {

@@ -18,7 +18,7 @@
 //   * split over the tiles so that 2-3 workgroups per CU exist; every workgroup writes its partial block once, a reduction kernel
 //     adds the slices in slice order (deterministic), wino_dfilter_kernel (winograd.hip) applies G^T . G.
 // Exact fp32 FMA chains; the association differs from the generic path (sums over 8192 tiles in other groupings).
-#include "common.h"
+#include "wino.h"
 #include "../../include/denet_hip.h"
 #include <stdlib.h>
 

@@ -31,7 +31,7 @@
 // cannot be consumed before the piece has landed. The next chunk's pieces are issued after component pair T_ISSUE of this
 // chunk's products: the fragment loads behind them are consumed T_D (three) pairs later at the earliest, and the consumption of the
 // last ones implies that the pieces have landed when the next transform starts.
-#include "common.h"
+#include "wino.h"
 #include "bn_final.h"
 #include "../../include/denet_hip.h"
 #include <stdlib.h>
@@ -172,8 +172,6 @@ __device__ __forceinline__ double t_row_ror(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), 0x120 + N, 0xF, 0xF, false);
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
-
-constexpr float T_AT[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 1, 1, 4, 4, 0}, {0, 1, -1, 8, -8, 1}};
 
 #ifdef T_TRACE
 #define T_STAMP() if (p.dbg && (blockIdx.x & 63) == 0 && tid == 0 && dbg_n < 32) p.dbg[(blockIdx.x >> 6) * 32 + dbg_n++] = __builtin_amdgcn_s_memtime()
@@ -372,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void wino4t_kernel(const W4TParams p) {
                 bool fst = true;
 #pragma unroll
                 for (int m = 0; m < 6; ++m) {
-                    const float c = T_AT[j][m];
+                    const float c = Wino<4>::AT[j][m];
                     if (c == 0.f) continue;
                     if (fst) a = c == 1.f ? acc[6 * l + m] : acc[6 * l + m] * c;
                     else if (c == 1.f) a += acc[6 * l + m];
@@ -390,7 +388,7 @@ __global__ __launch_bounds__(256, 2) void wino4t_kernel(const W4TParams p) {
                 bool fst = true;
 #pragma unroll
                 for (int l = 0; l < 6; ++l) {
-                    const float c = T_AT[i][l];
+                    const float c = Wino<4>::AT[i][l];
                     if (c == 0.f) continue;
                     if (fst) a = c == 1.f ? Z[l][j] : Z[l][j] * c;
                     else if (c == 1.f) a += Z[l][j];
@@ -574,15 +572,12 @@ extern "C" int denet_conv_wino4t_sums(const float* x, const float* u_packed, con
     }
     typedef void (*kern_t)(const W4TParams);
     static const kern_t kerns[3] = {wino4t_kernel<0>, wino4t_kernel<1>, wino4t_kernel<2>};
-    static bool attr_done[3] = {};
+    static bool attr_done[3][DENET_MAX_DEVICES] = {};
     const kern_t fn = kerns[ep];
-    if (!attr_done[ep]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-        if (e != hipSuccess) {
-            denet_set_error("conv_wino4t: hipFuncSetAttribute(%d B LDS): %s", T_LDS, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_done[ep] = true;
+    const hipError_t e = denet_allow_dynamic_lds((const void*)fn, 163840, attr_done[ep]);
+    if (e != hipSuccess) {
+        denet_set_error("conv_wino4t: hipFuncSetAttribute(%d B LDS): %s", T_LDS, hipGetErrorString(e));
+        return -(int)e;
     }
     // (experiments: DENET_W4T_LDS = LDS bytes requested per workgroup, e.g. 100000 leaves room for ONE workgroup per CU)
     static const int lds_req = [] { const char* e = getenv("DENET_W4T_LDS"); const int v = e ? atoi(e) : 0; return v > T_LDS && v <= 163840 ? v : T_LDS; }();

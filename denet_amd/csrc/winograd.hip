@@ -11,91 +11,12 @@
 // Filter gradient: dM = A dy A^T (wino_dout_kernel), dU[xi] = dM[xi]^T V[xi] (batched split-K product through the wgrad
 // kernel), dw = G^T dU G (wino_dfilter_kernel).
 // The data gradient of a stride-1 pad-1 3x3 convolution is the same convolution of dy with the taps rotated by 180
-// degrees and the channel roles swapped: wino_filter_kernel<true> writes U'[xi][c][k] from w[k][2-r][2-s][c].
-#include "common.h"
-#include <stdlib.h>
+// degrees and the channel roles swapped: wino_filter_dgrad_kernel writes U'[xi][c][k] from w[k][2-r][2-s][c].
+#include "wino.h"
+#include "bn_pointwise.h"
 #include "../../include/denet_hip.h"
 
-int denet_gemm_batched_nt(const float* a, const float* w, float* out, int batch, int M, int Nc, int Kc, long stride_a,
-                          long stride_w, long stride_out, hipStream_t stream);
-int denet_gemm_batched_tune(const float* a, const float* w, float* out, int batch, int M, int Nc, int Kc, long stride_a,
-                            long stride_w, long stride_out, hipStream_t stream);
-
-int denet_wgrad_batched(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int batch,
-                        int T, int Cc, int Kr, hipStream_t stream);
-int denet_wgrad_batched_tune(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int batch,
-                             int T, int Cc, int Kr, hipStream_t stream);
-
-// wino4f.hip: F(4x4) products + output transform in one kernel
-int denet_wino4f_block(int tile, long T, int C, int K);
-int denet_wino4f_stats_rows(int tb, long T);
-int denet_wino4f_run(int tb, const float* V, const float* U, const float* bias, const float* add, float* y, double* stats,
-                     const float* bs_x, const float* bs_y, const float* bs_gamma, const float* bs_beta, const float* bs_mean,
-                     const float* bs_invstd, int bs_relu, int N, int H, int W, int C, int K, int relu, hipStream_t stream);
-
-// wino4g.hip: F(4x4) filter-gradient component products + adjoint filter transform
-int denet_wino4g_splits(int tile, long T, int C, int K);
-size_t denet_wino4g_workspace_bytes(int splits, int C, int K);
-int denet_wino4g_run(int splits, const float* dM, const float* V, float* dU, float* part, size_t part_bytes, long T, int C, int K,
-                     hipStream_t stream);
-
 namespace {
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *(const f32x4*)p; }
-
-// ---- transform matrices (Lavin & Gray, "Fast algorithms for convolutional neural networks") -----------------
-// F(m x m, 3x3): TS = m + 2 points. Y = A^T [ (G g G^T) .* (B^T d B) ] A for the CORRELATION taps g.
-template <int MO>
-struct Wino;
-template <>
-struct Wino<2> {
-    static constexpr int TS = 4;
-    static constexpr float BT[4][4] = {{1, 0, -1, 0}, {0, 1, 1, 0}, {0, -1, 1, 0}, {0, 1, 0, -1}};
-    static constexpr float G[4][3] = {{1, 0, 0}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0, 0, 1}};
-    static constexpr float AT[2][4] = {{1, 1, 1, 0}, {0, 1, -1, -1}};
-};
-template <>
-struct Wino<4> {
-    static constexpr int TS = 6;
-    static constexpr float BT[6][6] = {{4, 0, -5, 0, 1, 0},  {0, -4, -4, 1, 1, 0}, {0, 4, -4, -1, 1, 0},
-                                       {0, -2, -1, 2, 1, 0}, {0, 2, -1, -2, 1, 0}, {0, 4, 0, -5, 0, 1}};
-    static constexpr float G[6][3] = {{0.25f, 0, 0},
-                                      {-1.f / 6, -1.f / 6, -1.f / 6},
-                                      {-1.f / 6, 1.f / 6, -1.f / 6},
-                                      {1.f / 24, 1.f / 12, 1.f / 6},
-                                      {1.f / 24, -1.f / 12, 1.f / 6},
-                                      {0, 0, 1}};
-    static constexpr float AT[4][6] = {{1, 1, 1, 1, 1, 0}, {0, 1, -1, 2, -2, 0}, {0, 1, 1, 4, 4, 0}, {0, 1, -1, 8, -8, 1}};
-};
-
-// one multiply-add of a transform, written as an explicit fused operation: left to the compiler, an expression like
-// 4*d0 - 5*d2 + d4 is contracted as fma(-5, d2, 4*d0) in one kernel and as fma(4, d0, -5*d2) in another (both legal, different
-// roundings) - with the explicit form every kernel that evaluates a transform produces the same bits (the transforms that
-// evaluate a batch norm on the fly, wino_prep_*, must equal wino_input_kernel / wino_dout_kernel exactly)
-__device__ __forceinline__ float wino_fma(float c, float v, float acc) { return __builtin_fmaf(c, v, acc); }
-__device__ __forceinline__ f32x4 wino_fma(float c, f32x4 v, f32x4 acc) {
-    f32x4 r;
-    r[0] = __builtin_fmaf(c, v[0], acc[0]);
-    r[1] = __builtin_fmaf(c, v[1], acc[1]);
-    r[2] = __builtin_fmaf(c, v[2], acc[2]);
-    r[3] = __builtin_fmaf(c, v[3], acc[3]);
-    return r;
-}
-
-// acc = sum_l coef[l] * v[l] with the compile-time coefficients folded (0 dropped): first product rounded, then one fused
-// multiply-add per further term, in index order
-#define WINO_DOT(acc, NL, COEF, VAL)                       \
-    {                                                      \
-        bool first_ = true;                                \
-        _Pragma("unroll") for (int l_ = 0; l_ < (NL); ++l_) { \
-            const float c_ = (COEF);                       \
-            if (c_ != 0.f) {                               \
-                if (first_) acc = c_ * (VAL);              \
-                else acc = wino_fma(c_, (VAL), acc);       \
-                first_ = false;                            \
-            }                                              \
-        }                                                  \
-    }
 
 // V[xi][t][c] = (B^T d B)[xi]: one thread per (tile, 4 channels); d = TS x TS input patch at (MO*ty-1, MO*tx-1).
 // up = 1: x is [N][H/2][W/2][C] and the layer's input is its 2 x 2 nearest-neighbour up-sampling (the pool-inverse layer in front,
@@ -125,28 +46,16 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict
             const bool ok = ((unsigned)iy < (unsigned)H) && ((unsigned)ix < (unsigned)W);
             d[i] = ok ? ld4(x + (((long)n * (H >> up) + (iy >> up)) * (W >> up) + (ix >> up)) * C + c4 * 4) : z;
         }
-#pragma unroll
-        for (int i = 0; i < TS; ++i) {
-            f32x4 acc = z;
-            WINO_DOT(acc, TS, WT::BT[i][l_], d[l_]);
-            tt[i][j] = acc;
-        }
+        wino_input_col<MO>(d, tt, j);
     }
-#pragma unroll
-    for (int i = 0; i < TS; ++i)
-#pragma unroll
-        for (int j = 0; j < TS; ++j) {
-            f32x4 acc = z;
-            WINO_DOT(acc, TS, WT::BT[j][l_], tt[i][l_]);
-            *(f32x4*)(V + ((long)(TS * i + j) * T + t) * C + c4 * 4) = acc;
-        }
+    wino_input_store<MO>(tt, V, T, t, C, c4 * 4);
 }
 
 // ---- transforms whose input is formed on the fly from a batch-norm layer -----------------------------------------------------
 // A Winograd pass that reads a tensor a batch norm has just written re-reads what a pointwise kernel produced one launch
-// earlier. These kernels evaluate the batch-norm expression while they gather the patch (same operations in the same order as
-// bn_apply_kernel / bn_bwd_apply_kernel of bn.hip, so every value is bit-identical to the separate passes) and write the tensor
-// the pointwise kernel would have written from the inner MO x MO pixels of each tile (each pixel belongs to exactly one tile):
+// earlier. wino_prep_lds_kernel evaluates the batch-norm expression while it gathers the patch (bn_pointwise.h: the text
+// bn_apply_kernel / bn_bwd_apply_kernel of bn.hip compile, so every value is bit-identical to the separate passes) and writes the
+// tensor the pointwise kernel would have written, each pixel once:
 //   FWD  d = relu?(fma(x, gamma*invstd, beta - mean*gamma*invstd) (+ res));  out = d (the activation);  V = B^T d B
 //        replaces bn_apply_kernel + wino_input_kernel of the next convolution (batch_norm_relu.py:34-48 -> convolution.py:80-83)
 //   BWD  g = dy masked by the ReLU (y > 0, or recomputed from x), d = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat));
@@ -167,122 +76,10 @@ struct BnFoldDev {
     int relu;
 };
 
-template <int MO, bool BWD>
-__global__ __launch_bounds__(256) void wino_prep_kernel(BnFoldDev f, float* __restrict__ V, float* __restrict__ dM, int N, int H,
-                                                        int W, int C, int TH, int TW, long T) {
-    using WT = Wino<MO>;
-    constexpr int TS = WT::TS;
-    const int c4n = C / 4;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= T * c4n) return;
-    const int c4 = (int)(idx % c4n);
-    const long t = idx / c4n;
-    const int tx = (int)(t % TW);
-    const int ty = (int)((t / TW) % TH);
-    const int n = (int)(t / ((long)TW * TH));
-    const int c = c4 * 4;
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    float mu[4], is[4], sc[4], sh[4], mg[4], mgx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mu[k] = f.mean[c + k];
-        is[k] = f.invstd[c + k];
-        sc[k] = f.gamma[c + k] * is[k];
-        sh[k] = (f.beta ? f.beta[c + k] : 0.f) - mu[k] * sc[k];
-        mg[k] = BWD ? f.coef[c + k] : 0.f;
-        mgx[k] = BWD ? f.coef[C + c + k] : 0.f;
-    }
-    // the value of the folded tensor at pixel (iy, ix); `inner`: this tile owns the pixel and writes `out`
-    auto value = [&](int iy, int ix, bool inner) -> f32x4 {
-        if (!(((unsigned)iy < (unsigned)H) && ((unsigned)ix < (unsigned)W))) return z;
-        const long o = (((long)n * H + iy) * W + ix) * C + c;
-        const f32x4 xv = ld4(f.x + o);
-        f32x4 d;
-        if (!BWD) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) d[k] = fmaf(xv[k], sc[k], sh[k]);
-            if (f.aux) d += ld4(f.aux + o);
-            if (f.relu) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) d[k] = fmaxf(d[k], 0.f);
-            }
-            if (inner) *(f32x4*)(f.out + o) = d;
-        } else {
-            f32x4 g = ld4(f.aux + o);
-            if (f.relu) {
-                if (f.y) {
-                    const f32x4 yv = ld4(f.y + o);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) g[k] = fmaf(xv[k], sc[k], sh[k]) > 0.f ? g[k] : 0.f;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xh = (xv[k] - mu[k]) * is[k];
-                d[k] = sc[k] * (g[k] - mg[k] - xh * mgx[k]);
-            }
-            if (inner && f.out) *(f32x4*)(f.out + o) = g;
-        }
-        return d;
-    };
-    {
-        f32x4 tt[TS][TS];       // B^T d, built column by column
-#pragma unroll
-        for (int j = 0; j < TS; ++j) {
-            const int ix = MO * tx - 1 + j;
-            f32x4 d[TS];
-#pragma unroll
-            for (int i = 0; i < TS; ++i) d[i] = value(MO * ty - 1 + i, ix, i >= 1 && i <= MO && j >= 1 && j <= MO);
-#pragma unroll
-            for (int i = 0; i < TS; ++i) {
-                f32x4 acc = z;
-                WINO_DOT(acc, TS, WT::BT[i][l_], d[l_]);
-                tt[i][j] = acc;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < TS; ++i)
-#pragma unroll
-            for (int j = 0; j < TS; ++j) {
-                f32x4 acc = z;
-                WINO_DOT(acc, TS, WT::BT[j][l_], tt[i][l_]);
-                *(f32x4*)(V + ((long)(TS * i + j) * T + t) * C + c) = acc;
-            }
-    }
-    if (BWD) {
-        // dM[xi][t][c] = (A d A^T)[xi] over the tile's own MO x MO pixels (wino_dout_kernel); the values are formed a second
-        // time from lines this thread has just read (cache hits) - keeping them through the first transform would spill
-        f32x4 a[TS][MO];
-#pragma unroll
-        for (int j = 0; j < MO; ++j) {
-            f32x4 d[MO];
-#pragma unroll
-            for (int i = 0; i < MO; ++i) d[i] = value(MO * ty + i, MO * tx + j, false);
-#pragma unroll
-            for (int i = 0; i < TS; ++i) {
-                f32x4 acc = z;
-                WINO_DOT(acc, MO, WT::AT[l_][i], d[l_]);
-                a[i][j] = acc;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < TS; ++i)
-#pragma unroll
-            for (int j = 0; j < TS; ++j) {
-                f32x4 acc = z;
-                WINO_DOT(acc, MO, WT::AT[l_][j], a[i][l_]);
-                *(f32x4*)(dM + ((long)(TS * i + j) * T + t) * C + c) = acc;
-            }
-    }
-}
-
-// The same passes with the patch staged through LDS: a workgroup owns a block of BT x BT tiles (BT*MO pixels square) and CQ
-// channel quads; it evaluates the folded tensor ONCE per pixel of the block + halo ((BT*MO+2)^2 pixels: 1.27x the block for
-// F(4x4), instead of the 2.25x of one-thread-per-tile gathers through L2, which made the version above slower than the passes
-// it replaces), writes the tensor the pointwise kernel would have written, and the threads then take their tiles from LDS.
+// The patch is staged through LDS: a workgroup owns a block of BT x BT tiles (BT*MO pixels square) and CQ channel quads; it
+// evaluates the folded tensor ONCE per pixel of the block + halo ((BT*MO+2)^2 pixels: 1.27x the block for F(4x4); a
+// one-thread-per-tile gather through L2 reads 2.25x and was 15-40 % slower than the passes it replaces), writes the tensor the
+// pointwise kernel would have written, and the threads then take their tiles from LDS.
 template <int MO, bool BWD>
 struct PrepLds {
     static constexpr int BT = 4;                    // tiles per block edge
@@ -312,16 +109,9 @@ __global__ __launch_bounds__(128) void wino_prep_lds_kernel(BnFoldDev f, float* 
     const int by = b % BH;
     const int n = b / BH;
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    float mu[4], is[4], sc[4], sh[4], mg[4], mgx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mu[k] = f.mean[c + k];
-        is[k] = f.invstd[c + k];
-        sc[k] = f.gamma[c + k] * is[k];
-        sh[k] = (f.beta ? f.beta[c + k] : 0.f) - mu[k] * sc[k];
-        mg[k] = BWD ? f.coef[c + k] : 0.f;
-        mgx[k] = BWD ? f.coef[C + c + k] : 0.f;
-    }
+    BnQuad bq;
+    bn_quad_load<false, true>(bq, f.gamma, f.beta, f.mean, f.invstd, c);
+    if (BWD) bn_quad_load_coef(bq, f.coef, C, c);
     // phase 1: the folded tensor over the block + halo, one pixel x channel quad per thread and round. The loads of a batch of
     // rounds are issued together, unconditionally (a pixel outside the image reads element 0 and is zeroed afterwards):
     // with 1.5 waves per SIMD the latency of a dependent load -> LDS chain per round was the whole kernel time
@@ -349,32 +139,14 @@ __global__ __launch_bounds__(128) void wino_prep_lds_kernel(BnFoldDev f, float* 
         }
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
-            f32x4 d = z;
+            f32x4 d;
             if (!BWD) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) d[k] = fmaf(xv[u][k], sc[k], sh[k]);
-                if (f.aux) d += av[u];
-                if (f.relu) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) d[k] = fmaxf(d[k], 0.f);
-                }
+                d = bn_forward(bq, xv[u], f.aux != nullptr, av[u], f.relu);
                 if (ok[u] && inner[u]) *(f32x4*)(f.out + off[u]) = d;
             } else {
                 f32x4 g = av[u];
-                if (f.relu) {
-                    if (f.y) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) g[k] = yv[u][k] > 0.f ? g[k] : 0.f;
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) g[k] = fmaf(xv[u][k], sc[k], sh[k]) > 0.f ? g[k] : 0.f;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float xh = (xv[u][k] - mu[k]) * is[k];
-                    d[k] = sc[k] * (g[k] - mg[k] - xh * mgx[k]);
-                }
+                if (f.relu) g = f.y ? bn_mask_y(g, yv[u]) : bn_mask_x(bq, g, xv[u]);
+                d = bn_backward(bq, g, xv[u]);
                 if (ok[u] && inner[u] && f.out) *(f32x4*)(f.out + off[u]) = g;
             }
             if (pix[u] < PP * PP) patch[pix[u] * PS + cq] = ok[u] ? d : z;
@@ -394,59 +166,32 @@ __global__ __launch_bounds__(128) void wino_prep_lds_kernel(BnFoldDev f, float* 
             f32x4 d[TS];
 #pragma unroll
             for (int i = 0; i < TS; ++i) d[i] = patch[((MO * tyl + i) * PP + MO * txl + j) * PS + cq];
-#pragma unroll
-            for (int i = 0; i < TS; ++i) {
-                f32x4 acc = z;
-                WINO_DOT(acc, TS, WT::BT[i][l_], d[l_]);
-                tt[i][j] = acc;
-            }
+            wino_input_col<MO>(d, tt, j);
         }
-#pragma unroll
-        for (int i = 0; i < TS; ++i)
-#pragma unroll
-            for (int j = 0; j < TS; ++j) {
-                f32x4 acc = z;
-                WINO_DOT(acc, TS, WT::BT[j][l_], tt[i][l_]);
-                *(f32x4*)(V + ((long)(TS * i + j) * T + t) * C + c) = acc;
-            }
+        wino_input_store<MO>(tt, V, T, t, C, c);
     }
     if (BWD) {
+        // dM[xi][t][c] = (A d A^T)[xi] over the tile's own MO x MO pixels (wino_dout_kernel)
         f32x4 a[TS][MO];
 #pragma unroll
         for (int j = 0; j < MO; ++j) {
             f32x4 d[MO];
 #pragma unroll
             for (int i = 0; i < MO; ++i) d[i] = patch[((MO * tyl + 1 + i) * PP + MO * txl + 1 + j) * PS + cq];
-#pragma unroll
-            for (int i = 0; i < TS; ++i) {
-                f32x4 acc = z;
-                WINO_DOT(acc, MO, WT::AT[l_][i], d[l_]);
-                a[i][j] = acc;
-            }
+            wino_dout_col<MO>(d, a, j);
         }
-#pragma unroll
-        for (int i = 0; i < TS; ++i)
-#pragma unroll
-            for (int j = 0; j < TS; ++j) {
-                f32x4 acc = z;
-                WINO_DOT(acc, MO, WT::AT[l_][j], a[i][l_]);
-                *(f32x4*)(dM + ((long)(TS * i + j) * T + t) * C + c) = acc;
-            }
+        wino_dout_store<MO>(a, dM, T, t, C, c);
     }
 }
 
 template <int MO, bool BWD>
 int launch_prep_lds(const BnFoldDev& f, float* V, float* dM, int N, int H, int W, int C, int TH, int TW, long T, hipStream_t stream) {
     using PL = PrepLds<MO, BWD>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute((const void*)wino_prep_lds_kernel<MO, BWD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)PL::LDS);
-        if (e != hipSuccess) {
-            denet_set_error("conv_wino fold: hipFuncSetAttribute(%zu B LDS): %s", PL::LDS, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_set[DENET_MAX_DEVICES] = {};
+    const hipError_t e = denet_allow_dynamic_lds((const void*)wino_prep_lds_kernel<MO, BWD>, (int)PL::LDS, attr_set);
+    if (e != hipSuccess) {
+        denet_set_error("conv_wino fold: hipFuncSetAttribute(%zu B LDS): %s", PL::LDS, hipGetErrorString(e));
+        return -(int)e;
     }
     const int BH = (TH + PL::BT - 1) / PL::BT, BW = (TW + PL::BT - 1) / PL::BT;
     hipLaunchKernelGGL((wino_prep_lds_kernel<MO, BWD>), dim3((unsigned)(N * BH * BW), (unsigned)(C / (4 * PL::CQ))), dim3(PL::NT),
@@ -454,8 +199,8 @@ int launch_prep_lds(const BnFoldDev& f, float* V, float* dM, int N, int H, int W
     return DENET_OK;
 }
 
-// U[xi][k][c] = (G g G^T)[xi] (DGRAD = false) or U'[xi][c][k] from the rotated taps (DGRAD = true); thread per (k, c)
-template <int MO, bool DGRAD>
+// U[xi][k][c] = (G g G^T)[xi]; thread per (k, c)
+template <int MO>
 __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restrict__ w, float* __restrict__ U, int K, int C) {
     using WT = Wino<MO>;
     constexpr int TS = WT::TS;
@@ -467,32 +212,20 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(const float* __restric
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int s = 0; s < 3; ++s) g[r][s] = w[(((long)k * 3 + (DGRAD ? 2 - r : r)) * 3 + (DGRAD ? 2 - s : s)) * C + c];
-    float a[TS][3];
-#pragma unroll
-    for (int i = 0; i < TS; ++i)
-#pragma unroll
-        for (int s = 0; s < 3; ++s) {
-            float acc = 0.f;
-            WINO_DOT(acc, 3, WT::G[i][l_], g[l_][s]);
-            a[i][s] = acc;
-        }
+        for (int s = 0; s < 3; ++s) g[r][s] = w[(((long)k * 3 + r) * 3 + s) * C + c];
+    float u[TS][TS];
+    wino_filter_transform<MO>(g, u);
     const long KC = (long)K * C;
-    const long o = DGRAD ? ((long)c * K + k) : ((long)k * C + c);
 #pragma unroll
     for (int i = 0; i < TS; ++i)
 #pragma unroll
-        for (int j = 0; j < TS; ++j) {
-            float acc = 0.f;
-            WINO_DOT(acc, 3, WT::G[j][l_], a[i][l_]);
-            U[(long)(TS * i + j) * KC + o] = acc;
-        }
+        for (int j = 0; j < TS; ++j) U[(long)(TS * i + j) * KC + (long)k * C + c] = u[i][j];
 }
 
 // Data-gradient filters U'[xi][c][k] from the rotated taps of w[k][r][s][c]: the (k, c) -> (c, k) transposition goes through
-// LDS so that global reads (16 consecutive c) and writes (16 consecutive k) both move 64-byte segments (the one-thread-per-
-// (k, c) form of wino_filter_kernel<MO, true> wrote 4-byte words K floats apart: 4x the time of the forward transform).
-// Block = 16 k x 16 c.
+// LDS so that global reads (16 consecutive c) and writes (16 consecutive k) both move 64-byte segments (a thread per (k, c)
+// that stores its own results writes 4-byte words K floats apart: 4x the time of the forward transform).
+// Block = 16 k x 16 c: K and C are multiples of 16 (the launchers check it).
 template <int MO>
 __global__ __launch_bounds__(256) void wino_filter_dgrad_kernel(const float* __restrict__ w, float* __restrict__ U, int K,
                                                                 int C) {
@@ -508,23 +241,12 @@ __global__ __launch_bounds__(256) void wino_filter_dgrad_kernel(const float* __r
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int q = 0; q < 3; ++q) g[r][q] = w[(((long)k * 3 + (2 - r)) * 3 + (2 - q)) * C + c];
-        float a[TS][3];
+        float u[TS][TS];
+        wino_filter_transform<MO>(g, u);
 #pragma unroll
         for (int i = 0; i < TS; ++i)
 #pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                float acc = 0.f;
-                WINO_DOT(acc, 3, WT::G[i][l_], g[l_][q]);
-                a[i][q] = acc;
-            }
-#pragma unroll
-        for (int i = 0; i < TS; ++i)
-#pragma unroll
-            for (int j = 0; j < TS; ++j) {
-                float acc = 0.f;
-                WINO_DOT(acc, 3, WT::G[j][l_], a[i][l_]);
-                tile[TS * i + j][cl][kl] = acc;
-            }
+            for (int j = 0; j < TS; ++j) tile[TS * i + j][cl][kl] = u[i][j];
     }
     __syncthreads();
     const long KC = (long)K * C;
@@ -561,32 +283,18 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
             f32x4 m[TS];
 #pragma unroll
             for (int i = 0; i < TS; ++i) m[i] = ld4(Mx + ((long)(TS * i + j) * T + t) * K + k4 * 4);
-#pragma unroll
-            for (int i = 0; i < MO; ++i) {
-                f32x4 acc = z;
-                WINO_DOT(acc, TS, WT::AT[i][l_], m[l_]);
-                s[i][j] = acc;
-            }
+            wino_output_col<MO>(m, s, j);
         }
         f32x4 b = z;
         if (bias) b = ld4(bias + k4 * 4);
-        float bs_mu[4] = {0.f, 0.f, 0.f, 0.f}, bs_is[4] = {0.f, 0.f, 0.f, 0.f}, bs_sc[4] = {0.f, 0.f, 0.f, 0.f}, bs_sh[4] = {0.f, 0.f, 0.f, 0.f};
-        if (bs.x) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                bs_mu[c] = bs.mean[k4 * 4 + c];
-                bs_is[c] = bs.invstd[k4 * 4 + c];
-                bs_sc[c] = (bs.gamma ? bs.gamma[k4 * 4 + c] : 1.f) * bs_is[c];
-                bs_sh[c] = (bs.beta ? bs.beta[k4 * 4 + c] : 0.f) - bs_mu[c] * bs_sc[c];
-            }
-        }
+        BnQuad bq = {};
+        if (bs.x) bn_quad_load<true, true>(bq, bs.gamma, bs.beta, bs.mean, bs.invstd, k4 * 4);
 #pragma unroll
         for (int i = 0; i < MO; ++i) {
             f32x4 ssum = z, ssq = z;
 #pragma unroll
             for (int j = 0; j < MO; ++j) {
-                f32x4 acc = z;
-                WINO_DOT(acc, TS, WT::AT[j][l_], s[i][l_]);
+                f32x4 acc = wino_output_at<MO>(s[i], j);
                 if (MO * ty + i >= H || MO * tx + j >= W) continue;     // a tile that reaches beyond the map: nothing stored or summed
                 const long o = (((long)n * H + MO * ty + i) * W + MO * tx + j) * K + k4 * 4;
                 acc += b;
@@ -603,19 +311,9 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restric
                     // masked by that layer's ReLU, sums of g and g * xhat
                     const f32x4 xv = ld4(bs.x + o);
                     f32x4 g = acc;
-                    if (bs.relu) {
-                        if (bs.y) {
-                            const f32x4 yv = ld4(bs.y + o);
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) g[c] = yv[c] > 0.f ? g[c] : 0.f;
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c) g[c] = fmaf(xv[c], bs_sc[c], bs_sh[c]) > 0.f ? g[c] : 0.f;
-                        }
-                    }
+                    if (bs.relu) g = bs.y ? bn_mask_y(g, ld4(bs.y + o)) : bn_mask_x(bq, g, xv);
                     ssum += g;
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) ssq[c] += g[c] * ((xv[c] - bs_mu[c]) * bs_is[c]);
+                    ssq += g * bn_xhat(bq, xv);
                 } else {
                     ssum += acc;
                     ssq += acc * acc;
@@ -687,21 +385,9 @@ __global__ __launch_bounds__(256) void wino_dout_kernel(const float* __restrict_
             const f32x4 v = ld4(dy + (((long)n * H + (in ? oy : 0)) * W + (in ? ox : 0)) * K + k4 * 4);
             d[i] = in ? v : z;
         }
-#pragma unroll
-        for (int i = 0; i < TS; ++i) {
-            f32x4 acc = z;
-            WINO_DOT(acc, MO, WT::AT[l_][i], d[l_]);
-            a[i][j] = acc;
-        }
+        wino_dout_col<MO>(d, a, j);
     }
-#pragma unroll
-    for (int i = 0; i < TS; ++i)
-#pragma unroll
-        for (int j = 0; j < TS; ++j) {
-            f32x4 acc = z;
-            WINO_DOT(acc, MO, WT::AT[l_][j], a[i][l_]);
-            *(f32x4*)(dM + ((long)(TS * i + j) * T + t) * K + k4 * 4) = acc;
-        }
+    wino_dout_store<MO>(a, dM, T, t, K, k4 * 4);
 }
 
 // filter gradient, step 3: dw[k][r][s][c] = (G^T dU G)[r][s], the adjoint of the filter transform
@@ -720,21 +406,14 @@ __global__ __launch_bounds__(256) void wino_dfilter_kernel(const float* __restri
         float u[TS];
 #pragma unroll
         for (int i = 0; i < TS; ++i) u[i] = dU[(long)(TS * i + j) * KC + (long)k * C + c];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            float acc = 0.f;
-            WINO_DOT(acc, TS, WT::G[l_][i], u[l_]);
-            r[i][j] = acc;
-        }
+        wino_dfilter_col<MO>(u, r, j);
     }
+    float g[3][3];
+    wino_dfilter_rows<MO>(r, g);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float acc = 0.f;
-            WINO_DOT(acc, TS, WT::G[l_][j], r[i][l_]);
-            dw[(((long)k * 3 + i) * 3 + j) * C + c] = acc;
-        }
+        for (int j = 0; j < 3; ++j) dw[(((long)k * 3 + i) * 3 + j) * C + c] = g[i][j];
 }
 
 struct WinoDims {
@@ -768,17 +447,12 @@ int wino_dims(int mo, int N, int H, int W, int C, int K, WinoDims* d) {
     }
 
 int wino_filter(int mo, bool dgrad, const float* w, float* U, int K, int C, hipStream_t stream) {
-    // w: [K,3,3,C]; forward: U[xi][K][C]; data gradient: U'[xi][C][K]
-    const unsigned fb = (unsigned)(((long)K * C + 255) / 256);
-    if (dgrad && K % 16 == 0 && C % 16 == 0) {
+    // w: [K,3,3,C]; forward: U[xi][K][C]; data gradient: U'[xi][C][K]. K, C: multiples of 16 (wino_dims, denet_conv_wino_filter)
+    if (dgrad) {
         if (mo == 2) hipLaunchKernelGGL(wino_filter_dgrad_kernel<2>, dim3(C / 16, K / 16), dim3(256), 0, stream, w, U, K, C);
         else hipLaunchKernelGGL(wino_filter_dgrad_kernel<4>, dim3(C / 16, K / 16), dim3(256), 0, stream, w, U, K, C);
-    } else if (dgrad) {
-        if (mo == 2) hipLaunchKernelGGL((wino_filter_kernel<2, true>), dim3(fb), dim3(256), 0, stream, w, U, K, C);
-        else hipLaunchKernelGGL((wino_filter_kernel<4, true>), dim3(fb), dim3(256), 0, stream, w, U, K, C);
     } else {
-        if (mo == 2) hipLaunchKernelGGL((wino_filter_kernel<2, false>), dim3(fb), dim3(256), 0, stream, w, U, K, C);
-        else hipLaunchKernelGGL((wino_filter_kernel<4, false>), dim3(fb), dim3(256), 0, stream, w, U, K, C);
+        WINO_LAUNCH(mo, wino_filter_kernel, (long)K * C, w, U, K, C);
     }
     DENET_CHECK_LAUNCH("conv_wino filter transform");
     return DENET_OK;
@@ -791,7 +465,7 @@ int wino_run(int mo, bool dgrad, const float* in, const float* w, const float* u
              hipStream_t stream, int relu = 0, double* stats = nullptr, const BnFoldDev* fold = nullptr, float* dm_out = nullptr,
              hipEvent_t transform_done = nullptr, const BnFoldDev* out_sums = nullptr, int in_up = 0) {
     // in: [N,H,W,Cin]   out: [N,H,W,Cout]   w: KRSC with (K,C) = dgrad ? (Cin,Cout) : (Cout,Cin)
-    // fold: the input is formed on the fly from a batch-norm layer (wino_prep_kernel; dgrad: backward form, dm_out receives dM)
+    // fold: the input is formed on the fly from a batch-norm layer (wino_prep_lds_kernel; dgrad: backward form, dm_out receives dM)
     DENET_CHECK_ARG((in || fold) && w && out && ws, "conv_wino: null pointer");
     WinoDims d;
     int rc = wino_dims(mo, N, H, W, Cin, Cout, &d);
@@ -809,24 +483,13 @@ int wino_run(int mo, bool dgrad, const float* in, const float* w, const float* u
         if (rc) return rc;
         U = Uw;
     }
-    static const int prep_lds = [] { const char* e = getenv("DENET_PREP_LDS"); return e ? atoi(e) : 1; }();
-    if (fold && prep_lds && Cin % 32 == 0 && (long)N * ((d.TH + 3) / 4) * ((d.TW + 3) / 4) < 0x7FFFFFFFL) {
+    if (fold) {
         DENET_CHECK_ARG(!dgrad || dm_out, "conv_wino: the backward fold needs the dM buffer");
         if (dgrad) rc = mo == 2 ? launch_prep_lds<2, true>(*fold, V, dm_out, N, H, W, Cin, d.TH, d.TW, d.T, stream)
                                 : launch_prep_lds<4, true>(*fold, V, dm_out, N, H, W, Cin, d.TH, d.TW, d.T, stream);
         else rc = mo == 2 ? launch_prep_lds<2, false>(*fold, V, nullptr, N, H, W, Cin, d.TH, d.TW, d.T, stream)
                           : launch_prep_lds<4, false>(*fold, V, nullptr, N, H, W, Cin, d.TH, d.TW, d.T, stream);
         if (rc) return rc;
-    } else if (fold) {
-        const unsigned blocks = (unsigned)((d.T * (Cin / 4) + 255) / 256);
-        if (dgrad) {
-            DENET_CHECK_ARG(dm_out, "conv_wino: the backward fold needs the dM buffer");
-            if (mo == 2) hipLaunchKernelGGL((wino_prep_kernel<2, true>), dim3(blocks), dim3(256), 0, stream, *fold, V, dm_out, N, H, W, Cin, d.TH, d.TW, d.T);
-            else hipLaunchKernelGGL((wino_prep_kernel<4, true>), dim3(blocks), dim3(256), 0, stream, *fold, V, dm_out, N, H, W, Cin, d.TH, d.TW, d.T);
-        } else {
-            if (mo == 2) hipLaunchKernelGGL((wino_prep_kernel<2, false>), dim3(blocks), dim3(256), 0, stream, *fold, V, (float*)nullptr, N, H, W, Cin, d.TH, d.TW, d.T);
-            else hipLaunchKernelGGL((wino_prep_kernel<4, false>), dim3(blocks), dim3(256), 0, stream, *fold, V, (float*)nullptr, N, H, W, Cin, d.TH, d.TW, d.T);
-        }
     } else {
         WINO_LAUNCH(mo, wino_input_kernel, d.T * (Cin / 4), in, V, N, H, W, Cin, d.TH, d.TW, d.T, in_up);
     }
@@ -887,7 +550,7 @@ static int wino_wgrad_run(const float* x, const float* dy, const float* dm_ready
         WINO_LAUNCH(tile, wino_input_kernel, d.T * (C / 4), x, Vw, N, H, W, C, d.TH, d.TW, d.T, 0);
         V = Vw;
     }
-    const float* dMr = dm_ready;       // already formed by the backward fold of the data-gradient call (wino_prep_kernel)
+    const float* dMr = dm_ready;       // already formed by the backward fold of the data-gradient call (wino_prep_lds_kernel)
     if (!dMr) {
         WINO_LAUNCH(tile, wino_dout_kernel, d.T * (K / 4), dy, dM, N, H, W, K, d.TH, d.TW, d.T);
         dMr = dM;
@@ -1076,6 +739,9 @@ extern "C" int denet_conv_wino_fwd_stats(const float* x, const float* w, const f
 // solver step): dgrad = 0: U[xi][K][C] for denet_conv_wino_fwd, 1: U'[xi][C][K] for denet_conv_wino_dgrad
 extern "C" int denet_conv_wino_filter(const float* w, float* u, int tile, int dgrad, int C, int K, hipStream_t stream) {
     DENET_CHECK_ARG(w && u && (tile == 2 || tile == 4) && C > 0 && K > 0, "conv_wino_filter: bad arguments");
+    // (wino_dims asks every pass of this file for multiples of 32; the reduction chunk of wino4t.hip, which also takes these
+    // filters, is 16 channels, and so is the block of wino_filter_dgrad_kernel)
+    DENET_CHECK_ARG(C % 16 == 0 && K % 16 == 0, "conv_wino_filter: the channel counts must be multiples of 16 (got C=%d K=%d)", C, K);
     return wino_filter(tile, dgrad != 0, w, u, K, C, stream);
 }
 

@@ -1539,8 +1539,9 @@ def bn_fwd_train(x, gamma, beta, run_mean, run_stdinv, momentum=0.9, eps=1e-5, r
 
 # ---- batch norm whose pointwise pass is left to the consumer (include/denet_hip.h: denet_bn_link) -------------------------------
 # Measured (round 3): the first form of the transform kernel (one thread per tile gathering the halo through L2 for two or three
-# tensors) was 15-40 % slower than the passes it replaced; with the patch staged through LDS and the loads of a batch of rounds
-# issued together it is faster: 965 -> 979 img/s for the whole step. DENET_BN_LINK=0 restores the separate passes.
+# tensors) was 15-40 % slower than the passes it replaced and is gone; with the patch staged through LDS and the loads of a batch
+# of rounds issued together (wino_prep_lds_kernel) it is faster: 965 -> 979 img/s for the whole step. DENET_BN_LINK=0 restores
+# the separate passes.
 LINK_BN = os.environ.get("DENET_BN_LINK", "1") != "0"
 
 
@@ -1589,7 +1590,8 @@ class BnLink:
     """A batch-norm layer that has reduced its statistics (forward) / its two gradient sums (backward) and leaves the pointwise
     pass to whoever reads the tensor next: a Winograd convolution evaluates it inside its input transform
     (denet_conv_wino_fwd_fold / denet_conv_wino_dgrad_fold), anybody else calls materialise(), which launches the very kernel
-    the batch norm would have launched (denet_bn_apply / denet_bn_bwd_apply). Values are bit-identical either way."""
+    the batch norm would have launched (denet_bn_apply / denet_bn_bwd_apply). Values are bit-identical either way: both sides
+    compile the expressions of csrc/bn_pointwise.h, and the transforms of csrc/wino.h."""
 
     def __init__(self, backward, x, aux, y, gamma, beta, mean, invstd, coef, relu, out=None):
         self.backward, self.x, self.aux, self.y = backward, x, aux, y

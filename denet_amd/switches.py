@@ -37,7 +37,6 @@ SWITCHES = {
     "DENET_BN_POOL_FUSE": ("1", "kernels", "the stem's BN + ReLU + max pool as one pass each way"),
     "DENET_BN_ACT_FUSE": ("1", "kernels", "`BN A` layer pairs run as the fused BN + ReLU"),
     "DENET_POOL_QUAD": ("1", "kernels", "the stem's backward pointwise pass on 2x2 pixel quads"),
-    "DENET_PREP_LDS": ("1", "kernels", "the linked transforms stage their block through LDS (0: one thread per tile)"),
     "DENET_SKIP_FUSE": ("1", "kernels", "SKIP additions in the epilogue of the convolution in front"),
     "DENET_UP_LINK": ("1", "kernels", "the pool-inverse layer read inside the next convolution's input transform"),
     "DENET_INFER_FOLD": ("1", "kernels", "inference: batch norm folded into the convolution in front of it"),

@@ -130,7 +130,9 @@ size_t denet_conv_wgrad_workspace_bytes(int N, int C, int K, int R, int S, int O
 size_t denet_conv_wino_workspace_bytes(int tile, int N, int H, int W, int C, int K);
 int denet_conv_wino_tune(float* workspace, size_t workspace_bytes, float* split_ws, size_t split_ws_bytes, int tile, int N,
                          int H, int W, int C, int K, hipStream_t stream);
-/* u_cached: transformed filters from denet_conv_wino_filter (dgrad = 0 / 1), or NULL to transform inside the call;
+/* u_cached: transformed filters from denet_conv_wino_filter (dgrad = 0: U[xi][K][C], 1: U'[xi][C][K] from the rotated taps;
+ * C, K multiples of 16 - the passes here need 32, the reduction of denet_conv_wino4t 16 - anything else is DENET_ERR_ARG and
+ * nothing is launched), or NULL to transform inside the call;
  * v_keep: [(m+2)^2 * tiles * C] buffer receiving the transformed input of the forward pass, v_cached: the same buffer
  * handed to the filter gradient of that layer (same tile), or NULL.                                             */
 int denet_conv_wino_filter(const float* w, float* u, int tile, int dgrad, int C, int K, hipStream_t stream);
@@ -245,7 +247,7 @@ size_t denet_conv_wgrad_bf16_workspace_bytes(int N, int C, int K, int R, int S, 
 int denet_conv_wgrad_bf16(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H, int W,
                           int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream);
 /* ---- Winograd passes whose input is formed on the fly from the batch-norm layer next to them (csrc/winograd.hip,
- *      wino_prep_kernel). Reference: the BN -> conv chains of the residual blocks (denet/layer/resnet.py:60-90,
+ *      wino_prep_lds_kernel). Reference: the BN -> conv chains of the residual blocks (denet/layer/resnet.py:60-90,
  *      batch_norm_relu.py:34-54): a pointwise pass writes a tensor the next convolution's input transform re-reads at once.
  *      denet_bn_link describes the batch norm; all values are bit-identical to the separate passes.
  *        forward  (denet_conv_wino_fwd_fold):  x = pre-normalisation tensor, aux = residual input or NULL, gamma / beta /

@@ -1427,3 +1427,126 @@ def test_conv_winograd_vs_direct(hip, shape, tile):
         rw = ops.conv_wgrad(x, dy, tuple(w.shape), stride=1, pad=1)
         gw = ops.conv_wino_wgrad(x, dy, tile=tile)
         assert float((rw - gw).abs().max()) <= 3 * tol * float(rw.abs().max())
+
+
+def _linked_case(case, tile, backward):
+    """random operands of a batch norm linked into the Winograd transforms of a 3x3 convolution C -> K on an N x H x W map; the
+    batch norm sits on the convolution's input (forward: C channels) or on its output gradient (backward: K channels)"""
+    N, H, W, C, K = case
+    gen = torch.Generator().manual_seed(sum(case) + 10 * tile + int(backward))
+    ch = K if backward else C
+    t = {"w": (torch.randn(K, 3, 3, C, generator=gen) * (2.0 / (9 * C)) ** 0.5).cuda(),
+         "x": torch.randn(N, H, W, ch, generator=gen).cuda(),        # the batch norm's input
+         "aux": torch.randn(N, H, W, ch, generator=gen).cuda(),      # forward: residual input; backward: gradient of its output
+         "y": torch.randn(N, H, W, ch, generator=gen).cuda(),        # backward: forward output (only its sign is read)
+         "xin": torch.randn(N, H, W, C, generator=gen).cuda(),       # backward: the convolution's input (filter gradient)
+         "gamma": (torch.rand(ch, generator=gen) + 0.5).cuda(), "beta": torch.randn(ch, generator=gen).cuda(),
+         "mean": (torch.randn(ch, generator=gen) * 0.3).cuda(), "invstd": (torch.rand(ch, generator=gen) + 0.5).cuda(),
+         "coef": (torch.randn(2, ch, generator=gen) * 0.1).cuda()}
+    return t
+
+
+_LINKED_CASES = [(2, 8, 8, 32, 32), (1, 20, 12, 64, 32), (2, 7, 10, 32, 64), (1, 32, 32, 64, 64)]
+
+
+@pytest.mark.parametrize("tile", [2, 4])
+@pytest.mark.parametrize("case", _LINKED_CASES)
+def test_linked_forward_transform_equals_the_separate_kernels(hip, case, tile):
+    """denet_conv_wino_fwd_fold (the batch norm in front evaluated inside the input transform, wino_prep_lds_kernel) against
+    denet_bn_apply + denet_conv_wino_fwd, through the C ABI, bit for bit: the activation, the transformed input V and y. Maps:
+    a 2 x 2 tile grid inside one 4 x 4 tile block; partial blocks on both axes with two channel blocks; a map that is no multiple
+    of either tile; full blocks. Plain, with ReLU, with ReLU and a residual input."""
+    import ctypes
+    from denet_amd import ops
+    N, H, W, C, K = case
+    t = _linked_case(case, tile, False)
+    L = ops._L()
+    T = N * -(-H // tile) * -(-W // tile)
+    nv = (tile + 2) ** 2 * T * C
+    ws = ops._wino_ws(tile, N, H, W, C, K)
+    for relu, res in ((0, 0), (1, 0), (1, 1)):
+        link = ops.BnLink(False, t["x"], t["aux"] if res else None, None, t["gamma"], t["beta"], t["mean"], t["invstd"], None, relu)
+        act = torch.full_like(t["x"], float("nan"))
+        v1, v2 = (torch.full((nv,), float("nan"), device="cuda") for _ in range(2))
+        y1, y2 = (torch.full((N, H, W, K), float("nan"), device="cuda") for _ in range(2))
+        bn = link.c_struct(act)
+        ops.check(L.denet_conv_wino_fwd_fold(ctypes.byref(bn), ops.ptr(t["w"]), None, ops.ptr(v1), None, None, ops.ptr(y1), 0, None, 0,
+                                             None, ops.ptr(ws), ws.numel(), tile, N, H, W, C, K, ops.stream_ptr()), "conv_wino_fwd_fold")
+        ref = link.materialise()
+        ops.check(L.denet_conv_wino_fwd(ops.ptr(ref), ops.ptr(t["w"]), None, ops.ptr(v2), None, None, ops.ptr(y2), ops.ptr(ws),
+                                        ws.numel(), tile, N, H, W, C, K, ops.stream_ptr()), "conv_wino_fwd")
+        assert torch.equal(act, ref), (relu, res)
+        assert torch.equal(v1, v2), (relu, res)
+        assert torch.equal(y1, y2), (relu, res)
+        assert bool(torch.isfinite(y1).all())
+
+
+@pytest.mark.parametrize("tile", [2, 4])
+@pytest.mark.parametrize("case", _LINKED_CASES)
+def test_linked_backward_transform_equals_the_separate_kernels(hip, case, tile):
+    """denet_conv_wino_dgrad_fold + denet_conv_wino_wgrad_dm (the backward pointwise pass of the batch norm behind the
+    convolution evaluated inside the transform kernel, which writes V and dM = A d A^T) against denet_bn_bwd_apply +
+    denet_conv_wino_dgrad + denet_conv_wino_wgrad, through the C ABI, bit for bit: dx, the residual-branch gradient, dw. Without
+    ReLU; with the mask recomputed from x; with the mask from the forward output (the last two with dres)."""
+    import ctypes
+    from denet_amd import ops
+    N, H, W, C, K = case
+    t = _linked_case(case, tile, True)
+    L = ops._L()
+    T = N * -(-H // tile) * -(-W // tile)
+    ws = ops._wino_ws(tile, N, H, W, C, K)
+    sws = ops.WS.get("wgrad", ops.WGRAD_WS_BYTES)
+    for relu, from_y, want_dres in ((0, 0, 0), (1, 0, 1), (1, 1, 1)):
+        def link(dres):
+            return ops.BnLink(True, t["x"], t["aux"], t["y"] if from_y else None, t["gamma"], t["beta"], t["mean"], t["invstd"],
+                              t["coef"], relu, out=dres)
+        dres1, dres2 = ((torch.full_like(t["x"], float("nan")) if want_dres else None) for _ in range(2))
+        dm = torch.full(((tile + 2) ** 2 * T * K,), float("nan"), device="cuda")
+        dx1, dx2 = (torch.full((N, H, W, C), float("nan"), device="cuda") for _ in range(2))
+        dw1, dw2 = (torch.full((K, 3, 3, C), float("nan"), device="cuda") for _ in range(2))
+        l1 = link(dres1)
+        bn = l1.c_struct(l1.out)
+        ops.check(L.denet_conv_wino_dgrad_fold(ctypes.byref(bn), ops.ptr(dm), ops.ptr(t["w"]), None, None, ops.ptr(dx1), None, None, 0,
+                                               None, ops.ptr(ws), ws.numel(), tile, N, H, W, C, K, None, ops.stream_ptr()),
+                  "conv_wino_dgrad_fold")
+        ops.check(L.denet_conv_wino_wgrad_dm(ops.ptr(t["xin"]), ops.ptr(dm), None, ops.ptr(dw1), ops.ptr(ws), ws.numel(), ops.ptr(sws),
+                                             sws.numel(), tile, N, H, W, C, K, ops.stream_ptr()), "conv_wino_wgrad_dm")
+        d = link(dres2).materialise()
+        ops.check(L.denet_conv_wino_dgrad(ops.ptr(d), ops.ptr(t["w"]), None, None, ops.ptr(dx2), ops.ptr(ws), ws.numel(), tile, N, H, W,
+                                          C, K, ops.stream_ptr()), "conv_wino_dgrad")
+        ops.check(L.denet_conv_wino_wgrad(ops.ptr(t["xin"]), ops.ptr(d), None, ops.ptr(dw2), ops.ptr(ws), ws.numel(), ops.ptr(sws),
+                                          sws.numel(), tile, N, H, W, C, K, ops.stream_ptr()), "conv_wino_wgrad")
+        assert torch.equal(dx1, dx2), (relu, from_y)
+        assert torch.equal(dw1, dw2), (relu, from_y)
+        if want_dres:
+            assert torch.equal(dres1, dres2), (relu, from_y)
+        assert bool(torch.isfinite(dx1).all()) and bool(torch.isfinite(dw1).all())
+
+
+@pytest.mark.parametrize("tile", [2, 4])
+@pytest.mark.parametrize("kc", [(32, 64), (96, 32)])
+def test_data_gradient_filters_are_the_transform_of_the_rotated_filters(hip, kc, tile):
+    """conv_wino_filter(dgrad=True), U'[xi][c][k] through the LDS transposition of wino_filter_dgrad_kernel, is bit for bit the
+    forward transform of the filters with the taps rotated by 180 degrees and the channel roles swapped"""
+    from denet_amd import ops
+    K, C = kc
+    gen = torch.Generator().manual_seed(K + C + tile)
+    w = torch.randn(K, 3, 3, C, generator=gen).cuda()
+    ud = ops.conv_wino_filter(w, tile, True)
+    uf = ops.conv_wino_filter(w.flip(1, 2).permute(3, 1, 2, 0).contiguous(), tile, False)
+    assert ud.numel() == uf.numel() == (tile + 2) ** 2 * K * C
+    assert torch.equal(ud.reshape(-1), uf.reshape(-1))
+
+
+def test_filter_transform_rejects_channel_counts_no_pass_accepts(hip):
+    """denet_conv_wino_filter with C = 24: DENET_ERR_ARG and a message, nothing launched (the buffer keeps its contents)"""
+    from denet_amd import ops
+    L = ops._L()
+    w = torch.randn(32, 3, 3, 24).cuda()
+    for tile in (2, 4):
+        for dgrad in (0, 1):
+            u = torch.full(((tile + 2) ** 2 * 32 * 24,), 7.0, device="cuda")
+            assert L.denet_conv_wino_filter(ops.ptr(w), ops.ptr(u), tile, dgrad, 24, 32, ops.stream_ptr()) == -1000
+            assert b"multiples" in L.denet_last_error()
+            torch.cuda.synchronize()
+            assert bool((u == 7.0).all())
