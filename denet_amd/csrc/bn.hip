@@ -569,11 +569,7 @@ extern "C" int denet_bn_relu_pool_fwd_train_xhat(const float* x, float* y_pool, 
 static void launch_pool_apply(const float* x, const float* dy_pool, const unsigned char* argmax, const float* gamma, const float* beta,
                               const float* save_mean, const float* save_invstd, const float* coef, float* dx, int N, int H, int W, int C,
                               int OH, int OW, int k, int stride, int pad, hipStream_t stream) {
-    static int quad = -1;
-    if (quad < 0) {
-        const char* e = getenv("DENET_POOL_QUAD");
-        quad = e ? atoi(e) : 1;
-    }
+    static const int quad = denet_env_int("DENET_POOL_QUAD", 1);
     if (quad && k == 3 && stride == 2 && pad == 1 && H % 2 == 0 && W % 2 == 0 && OH == H / 2 && OW == W / 2) {
         FastDiv fc, fow, foh;
         fc.init(C / 4); fow.init(OW); foh.init(OH);

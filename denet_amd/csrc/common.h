@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #define DENET_OK 0
 #define DENET_ERR_ARG (-1000)
@@ -45,6 +46,13 @@ static inline hipError_t denet_allow_dynamic_lds(const void* kernel, int bytes, 
     e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e == hipSuccess && known) done[dev] = true;
     return e;
+}
+
+// an integer switch of the environment: atoi of the variable when it is set, else `fallback`. A caller reads its switch once and
+// keeps the value in a static of its own.
+static inline int denet_env_int(const char* name, int fallback) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : fallback;
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -406,15 +406,11 @@ int launch_rect(RectParams& p, unsigned grid_y, hipStream_t stream) {
     constexpr int SZA = A_KIN ? BM * LDK : BK * (BM + 4);
     constexpr int SZB = B_KIN ? BN * LDK : BK * (BN + 4);
     constexpr size_t lds = 2 * (size_t)(SZA + SZB) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_rect_kernel<PASS, BM, BN, WM, WN>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            denet_set_error("conv_rect: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_set[DENET_MAX_DEVICES] = {};
+    const hipError_t e = denet_allow_dynamic_lds((const void*)conv_rect_kernel<PASS, BM, BN, WM, WN>, (int)lds, attr_set);
+    if (e != hipSuccess) {
+        denet_set_error("conv_rect: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+        return -(int)e;
     }
     p.tiles_m = ceil_div(p.M, BM);
     p.tiles_n = ceil_div(p.NC, BN);

@@ -438,7 +438,7 @@ extern "C" size_t denet_sparse_sort_workspace_bytes(int B, int H, int W, int roi
 namespace {
 // the one-kernel form (sparse_sort_image_kernel: one 1024-thread workgroup per image) serves this problem
 bool sort_is_single(const SortLayout& L) {
-    static const int one_kernel = [] { const char* e = getenv("DENET_SORT_ONE_KERNEL"); return e ? atoi(e) : 1; }();
+    static const int one_kernel = denet_env_int("DENET_SORT_ONE_KERNEL", 1);
     return one_kernel && L.HW <= 4096 && L.n <= 65535;
 }
 }  // namespace
@@ -465,30 +465,17 @@ extern "C" int denet_sparse_sort(const int* taps, void* sort_ws, size_t sort_ws_
     int* cell_start = order + L.off_start;
     int* table = order + L.off_table;
     const size_t lds = (size_t)L.HW * sizeof(int);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)sparse_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           32768 * 4);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)sparse_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 * 4);
-        if (e != hipSuccess) {
-            denet_set_error("sparse_sort: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_count[DENET_MAX_DEVICES] = {}, attr_scatter[DENET_MAX_DEVICES] = {}, attr_image[DENET_MAX_DEVICES] = {};
+    hipError_t e = denet_allow_dynamic_lds((const void*)sparse_count_kernel, 32768 * 4, attr_count);
+    if (e == hipSuccess) e = denet_allow_dynamic_lds((const void*)sparse_scatter_kernel, 32768 * 4, attr_scatter);
+    if (e == hipSuccess && sort_is_single(L))
+        e = denet_allow_dynamic_lds((const void*)sparse_sort_image_kernel, SORT1_WAVES * 4096 * 2, attr_image);
+    if (e != hipSuccess) {
+        denet_set_error("sparse_sort: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        return -(int)e;
     }
     if (sort_is_single(L)) {
         const size_t lds1 = (size_t)SORT1_WAVES * ((L.HW + 1) & ~1) * sizeof(unsigned short);
-        static bool attr1 = false;
-        if (!attr1) {
-            const hipError_t e = hipFuncSetAttribute((const void*)sparse_sort_image_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     SORT1_WAVES * 4096 * 2);
-            if (e != hipSuccess) {
-                denet_set_error("sparse_sort: hipFuncSetAttribute: %s", hipGetErrorString(e));
-                return -(int)e;
-            }
-            attr1 = true;
-        }
         hipLaunchKernelGGL(sparse_sort_image_kernel, dim3(B), dim3(1024), lds1, stream, taps, order, cell_start, L.n, L.HW, L.key_bits);
         DENET_CHECK_LAUNCH("sparse_sort");
         return DENET_OK;

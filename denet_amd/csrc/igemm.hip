@@ -85,6 +85,33 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, int elem_of
     return __builtin_bit_cast(f32x4, v);
 }
 
+// Issue order of one block of NM MFMAs inside the interleaved loops (sched_group_barrier): behind each of the first MFMAs the
+// scheduler slots one group - first the NR fragment reads of the next block, RP to a group, then NS staging passes: the LDS write
+// of a pass (WR) and / or its global load with VALU address instructions in front (LD) - and the remaining MFMAs follow in a row.
+template <int NM, int NR, int NS, bool WR, bool LD, int VALU>
+__device__ __forceinline__ void igemm_sched_block() {
+    constexpr int HALF = (NM / 2 > 0) ? NM / 2 : 1;
+    constexpr int RP = NR ? (NR + HALF - 1) / HALF : 1;
+    constexpr int RS = NR ? (NR + RP - 1) / RP : 0;
+    constexpr int SS = (NS < NM - RS) ? NS : ((NM - RS > 0) ? NM - RS : 0);
+#pragma unroll
+    for (int g = 0; g < RS; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, RP, 0);
+    }
+#pragma unroll
+    for (int g = 0; g < SS; ++g) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (WR) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+        if (LD) {
+            __builtin_amdgcn_sched_group_barrier(0x002, VALU, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        }
+    }
+    if constexpr (NM - RS - SS > 0) __builtin_amdgcn_sched_group_barrier(0x008, NM - RS - SS, 0);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 template <int MODE, int BM, int BN, int WM, int WN, int NBUF>
 __global__ __launch_bounds__(256, (NBUF == 1 ? (BM * BN <= 128 * 64 ? 4 : 3) : (NBUF == 2 ? 2 : 1))) void igemm_kernel(const IgemmParams p) {
     constexpr bool A_KIN = (MODE != MODE_WGRAD);
@@ -415,6 +442,20 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? (BM * BN <= 128 * 64 ? 4 : 3) : (
         }
     };
 
+    // the 4 x TM x TN matrix instructions of the 8-wide k block whose fragments are av / bv: the block of the two interleaved
+    // loops (compute() below keeps its own loop nest: called through here, igemm_kernel<2, 64, 64, 2, 2, 1> comes out of the
+    // compiler with another instruction order - as do the data-gradient kernels when store_chunk calls write_a / write_b or the
+    // two epilogues share the row decode, which therefore stay written out; EXPERIMENTS.md)
+    auto mma_block = [&](const float (&av)[TM][4], const float (&bv)[TN][4]) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[j][t], av[i][t], acc[i][j], 0, 0, 0);
+    };
+
     // a wave whose 32*TN columns lie entirely in the padding of the last N tile (e.g. wgrad of a 64-channel 3x3:
     // 576 = 4.5 x 128 columns) skips its matrix work; it still helps staging and keeps the barriers
     const bool wave_active = (n0 + wn * TN * 32 < p.NC) && (m0 + wm * TM * 32 < p.M);
@@ -481,34 +522,10 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? (BM * BN <= 128 * 64 ? 4 : 3) : (
                     if constexpr (kb < PB) {
                         if (do_l) load_b(kb);
                     }
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#pragma unroll
-                        for (int i = 0; i < TM; ++i)
-#pragma unroll
-                            for (int j = 0; j < TN; ++j)
-                                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[kb & 1][j][t], av[kb & 1][i][t],
-                                                                                 acc[i][j], 0, 0, 0);
-                    constexpr int NM = 4 * TM * TN;
+                    mma_block(av[kb & 1], bv[kb & 1]);
                     constexpr int NR = rd ? (A_KIN ? TM : 4 * TM) + (B_KIN ? TN : 4 * TN) : 0;
                     constexpr int NL = do_l ? ((kb < PA) ? 1 : 0) + ((kb < PB) ? 1 : 0) : 0;
-                    constexpr int HALF = (NM / 2 > 0) ? NM / 2 : 1;
-                    constexpr int RP = NR ? (NR + HALF - 1) / HALF : 1;
-                    constexpr int RS = NR ? (NR + RP - 1) / RP : 0;
-                    constexpr int LS = (NL < NM - RS) ? NL : ((NM - RS > 0) ? NM - RS : 0);
-#pragma unroll
-                    for (int g = 0; g < RS; ++g) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, RP, 0);
-                    }
-#pragma unroll
-                    for (int g = 0; g < LS; ++g) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x002, MODE == MODE_WGRAD ? 12 : 6, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                    if constexpr (NM - RS - LS > 0) __builtin_amdgcn_sched_group_barrier(0x008, NM - RS - LS, 0);
-                    __builtin_amdgcn_sched_barrier(0);
+                    igemm_sched_block<4 * TM * TN, NR, NL, false, true, (MODE == MODE_WGRAD ? 12 : 6)>();
                 };
                 step(std::integral_constant<int, 0>{});
                 step(std::integral_constant<int, 1>{});
@@ -575,38 +592,11 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? (BM * BN <= 128 * 64 ? 4 : 3) : (
                     if (do_w) write_b(wB, kb);
                     if (do_l) load_b(kb);
                 }
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv[kb & 1][j][t], av[kb & 1][i][t], acc[i][j],
-                                                                             0, 0, 0);
+                mma_block(av[kb & 1], bv[kb & 1]);
                 // issue order of this block
-                constexpr int NM = 4 * TM * TN;
                 constexpr int NR = rd ? (A_KIN ? TM : 4 * TM) + (B_KIN ? TN : 4 * TN) : 0;
                 constexpr int NW = do_w ? ((kb < PA) ? 1 : 0) + ((kb < PB) ? 1 : 0) : 0;
-                constexpr int HALF = (NM / 2 > 0) ? NM / 2 : 1;
-                constexpr int RP = NR ? (NR + HALF - 1) / HALF : 1;
-                constexpr int RS = NR ? (NR + RP - 1) / RP : 0;
-                constexpr int WS = (NW < NM - RS) ? NW : ((NM - RS > 0) ? NM - RS : 0);
-#pragma unroll
-                for (int g = 0; g < RS; ++g) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, RP, 0);
-                }
-#pragma unroll
-                for (int g = 0; g < WS; ++g) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                    if (do_l) {
-                        __builtin_amdgcn_sched_group_barrier(0x002, MODE == MODE_WGRAD ? 12 : 6, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                    }
-                }
-                if constexpr (NM - RS - WS > 0) __builtin_amdgcn_sched_group_barrier(0x008, NM - RS - WS, 0);
-                __builtin_amdgcn_sched_barrier(0);
+                igemm_sched_block<4 * TM * TN, NR, NW, true, do_l, (MODE == MODE_WGRAD ? 12 : 6)>();
             };
             step(std::integral_constant<int, 0>{});
             step(std::integral_constant<int, 1>{});
@@ -851,15 +841,11 @@ int launch_igemm(const IgemmParams& p, int splits, hipStream_t stream) {
     constexpr int SZA = A_KIN ? BM * LDK : BK * BM;
     constexpr int SZB = B_KIN ? BN * LDK : BK * BN;
     constexpr size_t lds = NBUF * (size_t)(SZA + SZB) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)igemm_kernel<MODE, BM, BN, WM, WN, NBUF>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            denet_set_error("igemm: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_set[DENET_MAX_DEVICES] = {};
+    const hipError_t e = denet_allow_dynamic_lds((const void*)igemm_kernel<MODE, BM, BN, WM, WN, NBUF>, (int)lds, attr_set);
+    if (e != hipSuccess) {
+        denet_set_error("igemm: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
+        return -(int)e;
     }
     // wgrad folds the split slices into grid.x (see the id decode in the kernel); dgrad: y = stride parity classes
     dim3 grid((unsigned)(p.tiles_m * p.tiles_n) * (MODE == MODE_WGRAD ? (unsigned)splits : 1u),
@@ -871,15 +857,19 @@ int launch_igemm(const IgemmParams& p, int splits, hipStream_t stream) {
     return DENET_OK;
 }
 
-#define LAUNCH_NBUF(MODE_, BM_, BN_, nbuf_, p_, splits_, stream_)                                        \
-    ((nbuf_) == 1   ? launch_igemm<MODE_, BM_, BN_, 2, 2, 1>(p_, splits_, stream_)                       \
-     : (nbuf_) == 2 ? launch_igemm<MODE_, BM_, BN_, 2, 2, 2>(p_, splits_, stream_)                       \
-                    : launch_igemm<MODE_, BM_, BN_, 2, 2, 3>(p_, splits_, stream_))
+// What a launch site runs: the tile shape, the loop structure (LDS buffers: 1, 2 or 3) and launch_igemm's `splits` (forward:
+// batch members, data gradients: parity classes, filter gradient: split slices). The plan_* functions below compute it from the
+// pass, the geometry, the workspace size and the process state (g_tuned, t_try, the DENET_* switches) and touch no HIP API:
+// denet_conv_plan answers without a device what the launch sites will run.
+struct IgemmPlan {
+    int bm, bn, nbuf, splits;
+};
 
-// Launch-shape selection. The chip runs 256 CUs x `cap` resident workgroups (cap = 2 with the double LDS buffer,
-// 3 with the single buffer); a grid that needs a partial extra round wastes up to a whole round. The launchers
-// price each candidate (tile, buffering) by rounds x tile area / relative tile efficiency and take the cheapest.
-// DENET_IGEMM_NBUF=1|2 forces the buffering (experiments).
+// the 12 geometry ints of the C ABI
+struct Geom {
+    int N, H, W, C, K, R, S, S_real, stride, pad, OH, OW;
+};
+
 // the batch norm whose sums this launch writes, if the caller armed it (bn_final.h): the last row tile of a column tile then reads
 // rows x bn columns x 16 bytes - taken over only while that stays below 1 MB (the head: 144 rows; a 64x64 map at batch 32 leaves
 // 1024 rows, which the separate kernel's C / 2 workgroups reduce faster than one workgroup could)
@@ -891,26 +881,10 @@ void take_final(IgemmParams& p, int bn, int classes) {
 }
 
 int forced_nbuf() {
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("DENET_IGEMM_NBUF");
-        forced = e ? atoi(e) : 0;
-    }
+    static const int forced = denet_env_int("DENET_IGEMM_NBUF", 0);
     return forced;
 }
 
-struct Choice {
-    double cost;
-    int tile;   // index of the tile candidate
-    int nbuf;
-};
-
-// nblocks[t]: grid size with tile candidate t; area[t]: BM*BN; eff[t]: relative MFMA efficiency of the tile.
-// Measured behaviour behind the rules: with >= 4 rounds of work the single-buffer variant streams ~12 % faster
-// (3 resident workgroups cover each other's barrier bubbles); for small grids what counts is the number of
-// rounds, and a half-size tile pays off only when the full tile cannot fill the chip once.
-// `want_nbuf`: the loop structure measured fastest for the mode / reduction length (see the callers); the tile shape
-// is then chosen for that structure's occupancy.
 // ---- measured launch configurations (denet_conv_tune) ---------------------------------------------------
 // key: mode + geometry; value: tile index, loop structure (NBUF) and, for wgrad, the round count that fixes the split
 struct TuneKey {
@@ -930,6 +904,10 @@ thread_local TuneVal t_try = {-1, 0, 0};     // candidate being timed by denet_c
 TuneKey tune_key(int mode, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad) {
     return TuneKey{{mode, N, H, W, C, K, R, S, S_real, stride, pad}};
 }
+TuneKey tune_key(int mode, const Geom& g) { return tune_key(mode, g.N, g.H, g.W, g.C, g.K, g.R, g.S, g.S_real, g.stride, g.pad); }
+// the batched products (modes 3 / 4) run a 1x1 geometry of one image row: its key carries the member count in place of N
+Geom batched_geom(int rows, int C, int K) { return Geom{1, 1, rows, C, K, 1, 1, 1, 1, 0, 1, rows}; }
+TuneKey batched_key(int mode, int batch, const Geom& g) { return tune_key(mode, batch, 1, g.W, g.C, g.K, 1, 1, 1, 1, 0); }
 
 // the configuration to use: the candidate under test, else a measured entry, else nothing (heuristics apply)
 bool tuned_choice(const TuneKey& k, TuneVal* out) {
@@ -944,14 +922,25 @@ bool tuned_choice(const TuneKey& k, TuneVal* out) {
 }
 
 int forced_tile() {      // DENET_IGEMM_TILE: 1 = first candidate (128x128), 2 = second (128x64); tuning aid
-    static int forced = -1;
-    if (forced < 0) {
-        const char* e = getenv("DENET_IGEMM_TILE");
-        forced = e ? atoi(e) : 0;
-    }
+    static const int forced = denet_env_int("DENET_IGEMM_TILE", 0);
     return forced;
 }
 
+// Launch-shape selection. The chip runs 256 CUs x `cap` resident workgroups (cap = 2 with the double LDS buffer,
+// 3 with the single buffer); a grid that needs a partial extra round wastes up to a whole round. Each candidate
+// (tile, buffering) is priced by rounds x tile area / relative tile efficiency and the cheapest taken.
+// DENET_IGEMM_NBUF=1|2 forces the buffering (experiments).
+// nblocks[t]: grid size with tile candidate t; area[t]: BM*BN; eff[t]: relative MFMA efficiency of the tile.
+// Measured behaviour behind the rules: with >= 4 rounds of work the single-buffer variant streams ~12 % faster
+// (3 resident workgroups cover each other's barrier bubbles); for small grids what counts is the number of
+// rounds, and a half-size tile pays off only when the full tile cannot fill the chip once.
+// `want_nbuf`: the loop structure measured fastest for the mode / reduction length (see the callers); the tile shape
+// is then chosen for that structure's occupancy.
+struct Choice {
+    double cost;
+    int tile;   // index of the tile candidate
+    int nbuf;
+};
 Choice choose_launch(const long* nblocks, const double* area, const double* eff, int ntiles, int want_nbuf) {
     Choice best = {1e300, 0, 2};
     for (int t = 0; t < ntiles; ++t) {
@@ -972,7 +961,9 @@ Choice choose_launch(const long* nblocks, const double* area, const double* eff,
     return best;
 }
 
-int check_geom(int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW) {
+int check_geom(const Geom& g) {
+    const int N = g.N, H = g.H, W = g.W, C = g.C, K = g.K, R = g.R, S = g.S, S_real = g.S_real, stride = g.stride, pad = g.pad,
+              OH = g.OH, OW = g.OW;
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "conv: non-positive dimension");
     DENET_CHECK_ARG(S_real > 0 && S_real <= S, "conv: S_real out of range");
     DENET_CHECK_ARG(ilog2_exact(stride) >= 0, "conv: stride must be a power of two (got %d)", stride);
@@ -993,32 +984,90 @@ int check_geom(int N, int H, int W, int C, int K, int R, int S, int S_real, int 
     return DENET_OK;
 }
 
-// split-K selection, launch and second-stage reduction of a weight-gradient problem described by `p` (p.M = K rows,
-// p.NC columns, p.npix reduction length, p.batch members sharing one launch)
-int wgrad_dispatch(IgemmParams& p, int K, float* dw, float* workspace, size_t workspace_bytes, const TuneKey& key,
-                   hipStream_t stream) {
-    p.ksteps = ceil_div(p.npix, BK);
-    const int batch = p.batch > 1 ? p.batch : 1;
-    int rc = DENET_OK;
+// ---- the plans: one rule per launch site, each exactly what that site has always run ----------------------------------------
+
+int plan_nbuf(int nbuf) { return nbuf == 1 ? 1 : (nbuf == 2 ? 2 : 3); }      // the loop structures there are: anything else runs 3
+
+// forward (`cols` = K, classes = 1) and data gradient (`cols` = C, classes = stride^2): tile 0 = 128 x 128, 1 = 128 x 64 priced by
+// choose_launch for the loop structure `want`; a measured record under `key` overrides both
+IgemmPlan plan_tiles(const TuneKey& key, long rows, int cols, int classes, int want) {
+    const long tm = ceil_div(rows, 128);
+    const long nb[2] = {tm * ceil_div(cols, 128) * classes, tm * ceil_div(cols, 64) * classes};
+    const double area[2] = {128.0 * 128.0, 128.0 * 64.0}, eff[2] = {1.0, 0.85};
+    Choice c = (cols >= 128) ? choose_launch(nb, area, eff, 2, want) : choose_launch(nb + 1, area + 1, eff + 1, 1, want);
+    int tile = (cols >= 128) ? c.tile : 1;
+    TuneVal tv;
+    if (tuned_choice(key, &tv)) {
+        tile = (cols >= 128) ? tv.tile : 1;
+        c.nbuf = tv.nbuf;
+    }
+    return IgemmPlan{128, tile == 0 ? 128 : 64, plan_nbuf(c.nbuf), classes};
+}
+
+// measured (tools/bench_conv.py): the pipelined 2-buffer loop wins on forward once the reduction has >= 24
+// chunks (+4...14 %); shorter reductions (stem, 64-channel 3x3, 1x1 on 128 channels) amortise its longer
+// prologue badly and run faster on the single-buffer loop at 3-4 workgroups per CU
+IgemmPlan plan_fwd(const Geom& g) {
+    const int ksteps = g.R * g.S * g.C / BK;
+    return plan_tiles(tune_key(MODE_FWD, g), (long)g.N * g.OH * g.OW, g.K, 1, ksteps >= 24 ? 2 : 1);
+}
+
+// the 1x1 stride-1 data gradient as a forward product over dy: it looks its record up under the FORWARD key with C and K swapped
+Geom swapped_1x1(const Geom& g) { return Geom{g.N, g.H, g.W, g.K, g.C, 1, 1, 1, 1, 0, g.H, g.W}; }
+IgemmPlan plan_dgrad_1x1t(const Geom& g) { return plan_fwd(swapped_1x1(g)); }
+
+IgemmPlan plan_dgrad(const Geom& g, bool transposed) {
+    const int classes = g.stride * g.stride;
+    const long rows = (long)g.N * (g.H / g.stride) * (g.W / g.stride);
+    if (!transposed) {
+        // dgrad / wgrad read K-outer LDS tiles (4x the fragment-read instructions): the single-buffer loop at 3-4
+        // workgroups per CU measured faster than the pipelined one on every DeNet-34 layer but two (within 3 %)
+        return plan_tiles(tune_key(MODE_DGRAD, g), rows, g.C, classes, 1);
+    }
+    // w is wt [R][S][C][K] (MODE_DGRAD_T): both operands reduction-contiguous, as in the forward pass - whose loop choice
+    // applies (the pipelined two-buffer loop from 24 chunks per parity class on); DENET_DGRAD_T_NBUF / _TILE: experiments
+    // (this rule of its own ignores the tuned table, t_try and choose_launch with its DENET_IGEMM_* switches)
+    static const int env_nbuf = denet_env_int("DENET_DGRAD_T_NBUF", 0);
+    static const int env_tile = denet_env_int("DENET_DGRAD_T_TILE", 0);
+    const int per_class = (g.R * g.S * g.K / BK) / classes;
+    const int nbuf = env_nbuf ? env_nbuf : (per_class >= 24 ? 2 : 1);
+    const long nb128 = (long)ceil_div(rows, 128) * ceil_div(g.C, 128) * classes;
+    const int wide = env_tile ? (env_tile == 1) : (g.C >= 128 && nbuf == 2 && nb128 >= 512);
+    return IgemmPlan{128, wide ? 128 : 64, plan_nbuf(nbuf), classes};
+}
+
+// batched GEMM out_b[M,Nc] = a_b[M,Kc] w_b[Nc,Kc]^T: a measured choice (denet_gemm_batched_tune) or: single-buffer loop for short
+// reductions, 128x64 when N is small or the 128x128 tiles of all members number fewer than 1024
+IgemmPlan plan_gemm_batched(int batch, const Geom& g) {
+    const int M = g.W, Kc = g.C, Nc = g.K;
+    int nbuf = (Kc / BK >= 24) ? 2 : 1;              // (the DENET_IGEMM_* forcing switches are not consulted here)
+    bool big = Nc >= 128 && (long)ceil_div(M, 128) * ceil_div(Nc, 128) * batch >= 1024;
+    TuneVal tv;
+    if (tuned_choice(batched_key(3, batch, g), &tv) && tv.nbuf < 10) {      // (>= 10: a stream-K record of round 2, skipped)
+        nbuf = tv.nbuf;
+        big = (tv.tile == 0) && Nc >= 128;
+    }
+    return IgemmPlan{128, big ? 128 : 64, plan_nbuf(nbuf), batch};
+}
+
+// filter gradient of `K` rows x `cols` columns over `npix` pixels, `batch` members sharing one launch, `ws_bytes` of split
+// workspace (0: none): the tile from the shape, loop structure and split slices from the price loop
+IgemmPlan plan_wgrad(const TuneKey& key, int K, int cols, int npix, int batch, size_t ws_bytes) {
+    const int ksteps = ceil_div(npix, BK);
     const bool big_m = (K >= 128);
     const int bm = big_m ? 128 : 64;
     // 64 x 64 tiles when the product has at most 64 columns (the batched filter-gradient products of the 64-channel Winograd
     // layers: dU[64][64]): with 128-wide tiles half of the waves would own nothing but padding
-    const bool narrow = !big_m && p.NC <= 64;
-    p.tiles_m = ceil_div(K, bm); p.tiles_n = ceil_div(p.NC, narrow ? 64 : 128);
-    const long wsize = (long)K * p.NC * batch;     // all batch members of one split slice
-    p.split_stride = wsize;
+    const bool narrow = !big_m && cols <= 64;
+    const int bn = narrow ? 64 : 128;
+    const long wsize = (long)K * cols * batch;     // all batch members of one split slice
     // Split-K selection. Every candidate (rounds r of a full chip, LDS buffering) fixes the number of slices so
     // that tiles x slices just fills r rounds; its price is r x (chunks per workgroup + fixed overhead) x chunk
     // time, plus the second-stage reduction that has to read slices x |dw| bytes. Measured constants: a 128x128
     // chunk takes ~4.2 us with 2 resident workgroups per CU and ~5.6 us with 3; HBM-side reduce ~3 TB/s.
-    const int tiles = p.tiles_m * p.tiles_n * batch;
-    const size_t max_by_ws = workspace ? workspace_bytes / ((size_t)wsize * sizeof(float)) : 0;
-    static int forced_blocks = -1;
-    if (forced_blocks < 0) {
-        const char* e = getenv("DENET_WGRAD_BLOCKS");
-        forced_blocks = e ? atoi(e) : 0;
-    }
+    const int tiles = ceil_div(K, bm) * ceil_div(cols, bn) * batch;
+    const size_t max_by_ws = ws_bytes / ((size_t)wsize * sizeof(float));
+    static const int forced_blocks = denet_env_int("DENET_WGRAD_BLOCKS", 0);
     int splits = 1, wg_nbuf = 2;
     {
         const double chunk_us2 = (big_m ? 4.2 : 2.4), chunk_us3 = chunk_us2 * 1.5 / 1.12;
@@ -1032,11 +1081,11 @@ int wgrad_dispatch(IgemmParams& p, int K, float* dw, float* workspace, size_t wo
                 if (have_tv && tv.rounds != r) continue;
                 int sp = forced_blocks ? ceil_div(forced_blocks, tiles) : (r * slots) / tiles;
                 if (sp < 1) sp = 1;
-                if (sp > p.ksteps / 4) sp = p.ksteps / 4 > 0 ? p.ksteps / 4 : 1;
+                if (sp > ksteps / 4) sp = ksteps / 4 > 0 ? ksteps / 4 : 1;
                 if (sp > 512) sp = 512;
                 if ((size_t)sp > max_by_ws && sp > 1) sp = max_by_ws > 0 ? (int)max_by_ws : 1;
-                const int per = ceil_div(p.ksteps, sp);
-                sp = ceil_div(p.ksteps, per);
+                const int per = ceil_div(ksteps, sp);
+                sp = ceil_div(ksteps, per);                // (the slices that are not empty)
                 const long nb = (long)tiles * sp;
                 const double rounds = (double)((nb + slots - 1) / slots);
                 const double t_main = rounds * (per + 2.0) * (nbuf == 1 ? chunk_us3 : chunk_us2);
@@ -1049,29 +1098,128 @@ int wgrad_dispatch(IgemmParams& p, int K, float* dw, float* workspace, size_t wo
             }
         }
     }
-    if (splits <= 1) {
-        splits = 1;
-        p.out = dw;
-    } else {
-        p.out = workspace;
-    }
-    p.steps_per_split = ceil_div(p.ksteps, splits);
-    splits = ceil_div(p.ksteps, p.steps_per_split);
-    if (big_m)
-        rc = LAUNCH_NBUF(MODE_WGRAD, 128, 128, wg_nbuf, p, splits, stream);
-    else if (narrow)
-        rc = LAUNCH_NBUF(MODE_WGRAD, 64, 64, wg_nbuf, p, splits, stream);
-    else
-        rc = LAUNCH_NBUF(MODE_WGRAD, 64, 128, wg_nbuf, p, splits, stream);
+    return IgemmPlan{bm, bn, wg_nbuf, splits};
+}
+
+// ---- the launcher: tiles of the plan's shape, the batch norm's final reduction where the epilogue writes sums, the instantiation
+template <int MODE, int BM, int BN>
+int launch_tile(IgemmParams& p, const IgemmPlan& plan, hipStream_t stream) {
+    p.tiles_m = ceil_div(p.M, BM);
+    p.tiles_n = ceil_div(p.NC, BN);
+    if (MODE != MODE_WGRAD) take_final(p, BN, plan.splits);     // (splits = parity classes; a batched GEMM has no sums: no-op)
+    if (plan.nbuf == 1) return launch_igemm<MODE, BM, BN, 2, 2, 1>(p, plan.splits, stream);
+    if (plan.nbuf == 2) return launch_igemm<MODE, BM, BN, 2, 2, 2>(p, plan.splits, stream);
+    return launch_igemm<MODE, BM, BN, 2, 2, 3>(p, plan.splits, stream);
+}
+
+// forward and both data gradients: 128 x 128 or 128 x 64
+template <int MODE>
+int launch_plan(IgemmParams& p, const IgemmPlan& plan, hipStream_t stream) {
+    if (plan.bn == 128) return launch_tile<MODE, 128, 128>(p, plan, stream);
+    return launch_tile<MODE, 128, 64>(p, plan, stream);
+}
+
+// filter gradient: 128 x 128, 64 x 64 or 64 x 128
+int launch_plan_wgrad(IgemmParams& p, const IgemmPlan& plan, hipStream_t stream) {
+    if (plan.bm == 128) return launch_tile<MODE_WGRAD, 128, 128>(p, plan, stream);
+    if (plan.bn == 64) return launch_tile<MODE_WGRAD, 64, 64>(p, plan, stream);
+    return launch_tile<MODE_WGRAD, 64, 128>(p, plan, stream);
+}
+
+// the geometry half of the parameters; a pass adds its operands, M / NC / ksteps, the byte extents and the divisors
+IgemmParams conv_params(const Geom& g) {
+    IgemmParams p = {};
+    p.N = g.N; p.H = g.H; p.W = g.W; p.C = g.C; p.OH = g.OH; p.OW = g.OW; p.K = g.K;
+    p.R = g.R; p.S = g.S; p.S_real = g.S_real; p.stride = g.stride; p.sshift = ilog2_exact(g.stride); p.pad = g.pad;
+    return p;
+}
+
+// the column sums of the epilogue become the backward reductions of the batch norm `bn`
+void set_bn_sums(IgemmParams& p, const denet_bn_link& bn) {
+    p.bs_x = bn.x; p.bs_y = bn.relu ? bn.y : nullptr; p.bs_gamma = bn.gamma; p.bs_beta = bn.beta;
+    p.bs_mean = bn.mean; p.bs_invstd = bn.invstd; p.bs_relu = bn.relu;
+}
+
+// a data gradient's request for those sums (entry point `who`): refuses an incomplete one; *stats_rows = stride^2 (parity classes)
+// x row tiles of a class and *ok when the geometry divides and the buffer holds the rows, else 0 rows and no sums
+int sums_request(const char* who, const denet_bn_link* sums_of, double* stats_partial, size_t stats_bytes, int* stats_rows, int N,
+                 int H, int W, int C, int stride, bool* ok) {
+    DENET_CHECK_ARG(sums_of && stats_partial && stats_rows, "%s: null pointer", who);
+    DENET_CHECK_ARG(sums_of->x && sums_of->mean && sums_of->invstd && (!sums_of->relu || sums_of->y || (sums_of->gamma && sums_of->beta)),
+                    "%s: incomplete batch-norm description", who);
+    const bool geom = stride >= 1 && H % stride == 0 && W % stride == 0;
+    const long rows = geom ? (long)stride * stride * (((long)N * (H / stride) * (W / stride) + 127) / 128) : 0;
+    *ok = geom && stats_bytes >= (size_t)rows * 2 * C * sizeof(double);
+    *stats_rows = *ok ? (int)rows : 0;
+    return DENET_OK;
+}
+
+// launch and second-stage reduction of a weight-gradient problem described by `p` (p.M = K rows, p.NC columns, p.npix
+// reduction length, p.batch members sharing one launch)
+int wgrad_dispatch(IgemmParams& p, float* dw, float* workspace, size_t workspace_bytes, const TuneKey& key, hipStream_t stream) {
+    const int batch = p.batch > 1 ? p.batch : 1;
+    const IgemmPlan plan = plan_wgrad(key, p.M, p.NC, p.npix, batch, workspace ? workspace_bytes : 0);
+    const long wsize = (long)p.M * p.NC * batch;
+    p.ksteps = ceil_div(p.npix, BK);
+    p.steps_per_split = ceil_div(p.ksteps, plan.splits);
+    p.split_stride = wsize;
+    p.out = plan.splits > 1 ? workspace : dw;
+    const int rc = launch_plan_wgrad(p, plan, stream);
     if (rc) return rc;
-    if (splits > 1) {
+    if (plan.splits > 1) {
         DENET_CHECK_ARG(wsize % 4 == 0, "conv_wgrad: weight size not a multiple of 4");
         long n4 = wsize / 4;
         int blocks = (int)((n4 + 63) / 64);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, workspace, dw, n4, splits, n4);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, workspace, dw, n4, plan.splits, n4);
         DENET_CHECK_LAUNCH("splitk_reduce");
     }
     return DENET_OK;
+}
+
+// Warm-up plus the fastest of 3 timed runs of `run` for every candidate (installed in t_try, which every plan consults first);
+// *best = the fastest, the first on ties. Profiling is off meanwhile, the first error ends the loop, and t_try, the profiling
+// switch and both events are put back on every path. Synchronises the stream.
+template <class Run>
+int time_candidates(const char* who, const std::vector<TuneVal>& cand, hipStream_t stream, Run run, TuneVal* best) {
+    hipEvent_t e0, e1;
+    if (hipEventCreate(&e0) != hipSuccess) {
+        denet_set_error("%s: hipEventCreate failed", who);
+        return DENET_ERR_ARG;
+    }
+    if (hipEventCreate(&e1) != hipSuccess) {
+        (void)hipEventDestroy(e0);
+        denet_set_error("%s: hipEventCreate failed", who);
+        return DENET_ERR_ARG;
+    }
+    const bool prof_was_on = g_prof_on;
+    g_prof_on = false;
+    float best_ms = 1e30f;
+    *best = cand[0];
+    int rc = DENET_OK;
+    for (const TuneVal& c : cand) {
+        t_try = c;
+        rc = run();                                  // warm-up (also sets the LDS attribute of the instantiation)
+        float ms_min = 1e30f;
+        for (int rep = 0; rep < 3 && !rc; ++rep) {
+            (void)hipEventRecord(e0, stream);
+            rc = run();
+            (void)hipEventRecord(e1, stream);
+            if (hipEventSynchronize(e1) != hipSuccess) rc = DENET_ERR_ARG;
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            if (ms < ms_min) ms_min = ms;
+        }
+        if (rc) break;
+        if (ms_min < best_ms) {
+            best_ms = ms_min;
+            *best = c;
+        }
+    }
+    t_try = TuneVal{-1, 0, 0};
+    g_prof_on = prof_was_on;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
 }
 
 }  // namespace
@@ -1120,29 +1268,14 @@ int denet_gemm_batched_nt(const float* a, const float* w, float* out, int batch,
     DENET_CHECK_ARG(a && w && out && batch > 0 && batch <= 65535 && M > 0, "gemm_batched: bad arguments");
     DENET_CHECK_ARG(Nc % 32 == 0 && Kc % 32 == 0, "gemm_batched: Nc, Kc must be multiples of 32");
     DENET_CHECK_ARG((long)M * Kc * 4 < 0xF0000000L && (long)Nc * Kc * 4 < 0xF0000000L, "gemm_batched: operand too large");
-    IgemmParams p = {};
+    const Geom g = batched_geom(M, Kc, Nc);
+    IgemmParams p = conv_params(g);
     p.act = a; p.wgt = w; p.out = out;
-    p.N = 1; p.H = 1; p.W = M; p.C = Kc; p.OH = 1; p.OW = M; p.K = Nc;
-    p.R = 1; p.S = 1; p.S_real = 1; p.stride = 1; p.sshift = 0; p.pad = 0;
     p.act_bytes = (unsigned)((size_t)M * Kc * 4); p.wgt_bytes = (unsigned)((size_t)Nc * Kc * 4);
     p.batch_act = stride_a; p.batch_wgt = stride_w; p.batch_out = stride_out;
     p.M = M; p.NC = Nc; p.ksteps = Kc / BK; p.steps_per_split = p.ksteps; p.npix = M;
     p.div_row_hw.init(M); p.div_row_w.init(M);
-    p.tiles_m = ceil_div(M, 128);
-    // measured choice (denet_gemm_batched_tune) or: single-buffer loop for short reductions, 128x64 when N is small
-    int nbuf = (p.ksteps >= 24) ? 2 : 1;
-    bool big = Nc >= 128 && (long)p.tiles_m * ceil_div(Nc, 128) * batch >= 1024;
-    TuneVal tv;
-    if (tuned_choice(tune_key(3, batch, 1, M, Kc, Nc, 1, 1, 1, 1, 0), &tv) && tv.nbuf < 10) {      // (>= 10: a stream-K record of round 2)
-        nbuf = tv.nbuf;
-        big = (tv.tile == 0) && Nc >= 128;
-    }
-    if (big) {
-        p.tiles_n = ceil_div(Nc, 128);
-        return LAUNCH_NBUF(MODE_FWD, 128, 128, nbuf, p, batch, stream);
-    }
-    p.tiles_n = ceil_div(Nc, 64);
-    return LAUNCH_NBUF(MODE_FWD, 128, 64, nbuf, p, batch, stream);
+    return launch_plan<MODE_FWD>(p, plan_gemm_batched(batch, g), stream);
 }
 
 // Batch of `batch` independent products dw_b[Kr,Cc] = sum_t dy_b[t,Kr] * x_b[t,Cc] (row-major, t = reduction) through
@@ -1152,56 +1285,28 @@ int denet_wgrad_batched(const float* x, const float* dy, float* dw, float* works
     DENET_CHECK_ARG(x && dy && dw && batch > 0 && batch <= 65535 && T > 0, "wgrad_batched: bad arguments");
     DENET_CHECK_ARG(Cc % 32 == 0 && Kr % 32 == 0, "wgrad_batched: channel counts must be multiples of 32");
     DENET_CHECK_ARG((long)T * Cc * 4 < 0xF0000000L && (long)T * Kr * 4 < 0xF0000000L, "wgrad_batched: operand too large");
-    IgemmParams p = {};
+    const Geom g = batched_geom(T, Cc, Kr);
+    IgemmParams p = conv_params(g);
     p.act = x; p.wgt = dy;
-    p.N = 1; p.H = 1; p.W = T; p.C = Cc; p.OH = 1; p.OW = T; p.K = Kr;
-    p.R = 1; p.S = 1; p.S_real = 1; p.stride = 1; p.sshift = 0; p.pad = 0;
     p.act_bytes = (unsigned)((size_t)T * Cc * 4); p.wgt_bytes = (unsigned)((size_t)T * Kr * 4);
     p.batch = batch; p.batch_act = (long)T * Cc; p.batch_wgt = (long)T * Kr; p.batch_out = (long)Kr * Cc;
     p.M = Kr; p.NC = Cc; p.npix = T;
     p.wg_split_slow = 1;
     p.div_row_hw.init(T); p.div_row_w.init(T);
-    return wgrad_dispatch(p, Kr, dw, workspace, workspace_bytes, tune_key(4, batch, 1, T, Cc, Kr, 1, 1, 1, 1, 0), stream);
+    return wgrad_dispatch(p, dw, workspace, workspace_bytes, batched_key(4, batch, g), stream);
 }
 
 // measures the split / loop structure of the batched weight-gradient product (synchronises the stream)
 int denet_wgrad_batched_tune(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int batch,
                              int T, int Cc, int Kr, hipStream_t stream) {
-    const TuneKey key = tune_key(4, batch, 1, T, Cc, Kr, 1, 1, 1, 1, 0);
+    const TuneKey key = batched_key(4, batch, batched_geom(T, Cc, Kr));
     if (g_tuned.count(key)) return DENET_OK;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        denet_set_error("wgrad_batched_tune: hipEventCreate failed");
-        return DENET_ERR_ARG;
-    }
-    const bool prof_was_on = g_prof_on;
-    g_prof_on = false;
-    float best_ms = 1e30f;
-    TuneVal best = {0, 1, 1};
-    int rc = DENET_OK;
-    for (int nbuf = 1; nbuf <= 2 && !rc; ++nbuf)
-        for (int r = 1; r <= (nbuf == 1 ? 6 : 3) && !rc; ++r) {
-            t_try = TuneVal{0, nbuf, r};
-            rc = denet_wgrad_batched(x, dy, dw, workspace, workspace_bytes, batch, T, Cc, Kr, stream);
-            float ms_min = 1e30f;
-            for (int rep = 0; rep < 3 && !rc; ++rep) {
-                (void)hipEventRecord(e0, stream);
-                rc = denet_wgrad_batched(x, dy, dw, workspace, workspace_bytes, batch, T, Cc, Kr, stream);
-                (void)hipEventRecord(e1, stream);
-                if (hipEventSynchronize(e1) != hipSuccess) rc = DENET_ERR_ARG;
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, e0, e1);
-                if (ms < ms_min) ms_min = ms;
-            }
-            if (!rc && ms_min < best_ms) {
-                best_ms = ms_min;
-                best = t_try;
-            }
-        }
-    t_try = TuneVal{-1, 0, 0};
-    g_prof_on = prof_was_on;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    std::vector<TuneVal> cand;
+    for (int nbuf = 1; nbuf <= 2; ++nbuf)
+        for (int r = 1; r <= (nbuf == 1 ? 6 : 3); ++r) cand.push_back(TuneVal{0, nbuf, r});
+    TuneVal best;
+    const int rc = time_candidates("wgrad_batched_tune", cand, stream, [&] {
+        return denet_wgrad_batched(x, dy, dw, workspace, workspace_bytes, batch, T, Cc, Kr, stream); }, &best);
     if (rc) return rc;
     g_tuned[key] = best;
     return DENET_OK;
@@ -1210,45 +1315,14 @@ int denet_wgrad_batched_tune(const float* x, const float* dy, float* dw, float* 
 // measures the launch configuration of the batched GEMM for these sizes (synchronises the stream)
 int denet_gemm_batched_tune(const float* a, const float* w, float* out, int batch, int M, int Nc, int Kc, long stride_a,
                             long stride_w, long stride_out, hipStream_t stream) {
-    const TuneKey key = tune_key(3, batch, 1, M, Kc, Nc, 1, 1, 1, 1, 0);
+    const TuneKey key = batched_key(3, batch, batched_geom(M, Kc, Nc));
     if (g_tuned.count(key)) return DENET_OK;
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        denet_set_error("gemm_batched_tune: hipEventCreate failed");
-        return DENET_ERR_ARG;
-    }
-    const bool prof_was_on = g_prof_on;
-    g_prof_on = false;
-    float best_ms = 1e30f;
-    TuneVal best = {1, 1, 0};
-    int rc = DENET_OK;
     std::vector<TuneVal> cand;
-    for (int t = (Nc >= 128 ? 0 : 1); t < 2; ++t) {
+    for (int t = (Nc >= 128 ? 0 : 1); t < 2; ++t)
         for (int nbuf = 1; nbuf <= 2; ++nbuf) cand.push_back(TuneVal{t, nbuf, 0});
-    }
-    for (const TuneVal& c : cand) {
-        if (rc) break;
-        t_try = c;
-        rc = denet_gemm_batched_nt(a, w, out, batch, M, Nc, Kc, stride_a, stride_w, stride_out, stream);
-        float ms_min = 1e30f;
-        for (int rep = 0; rep < 3 && !rc; ++rep) {
-            (void)hipEventRecord(e0, stream);
-            rc = denet_gemm_batched_nt(a, w, out, batch, M, Nc, Kc, stride_a, stride_w, stride_out, stream);
-            (void)hipEventRecord(e1, stream);
-            if (hipEventSynchronize(e1) != hipSuccess) rc = DENET_ERR_ARG;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            if (ms < ms_min) ms_min = ms;
-        }
-        if (!rc && ms_min < best_ms) {
-            best_ms = ms_min;
-            best = t_try;
-        }
-    }
-    t_try = TuneVal{-1, 0, 0};
-    g_prof_on = prof_was_on;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    TuneVal best;
+    const int rc = time_candidates("gemm_batched_tune", cand, stream, [&] {
+        return denet_gemm_batched_nt(a, w, out, batch, M, Nc, Kc, stride_a, stride_w, stride_out, stream); }, &best);
     if (rc) return rc;
     g_tuned[key] = best;
     return DENET_OK;
@@ -1269,6 +1343,7 @@ extern "C" int denet_conv_tune(int mode, const float* a, const float* b, const f
         if (mode == MODE_DGRAD) return denet_conv_dgrad(a, b, add, out, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW, stream);
         return denet_conv_wgrad(a, b, out, workspace, workspace_bytes, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW, stream);
     };
+    if (g_tuned.count(key)) return run();            // measured (or imported) already: not again, `out` still gets the result
     std::vector<TuneVal> cand;
     if (mode == MODE_WGRAD) {
         for (int r = 1; r <= 6; ++r) cand.push_back(TuneVal{0, 1, r});
@@ -1278,40 +1353,8 @@ extern "C" int denet_conv_tune(int mode, const float* a, const float* b, const f
         for (int t = (ndim >= 128 ? 0 : 1); t < 2; ++t)
             for (int nbuf = 1; nbuf <= 2; ++nbuf) cand.push_back(TuneVal{t, nbuf, 0});
     }
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        denet_set_error("conv_tune: hipEventCreate failed");
-        return DENET_ERR_ARG;
-    }
-    const bool prof_was_on = g_prof_on;
-    g_prof_on = false;
-    float best_ms = 1e30f;
-    TuneVal best = cand[0];
-    int rc = DENET_OK;
-    for (const TuneVal& c : cand) {
-        t_try = c;
-        rc = run();                                  // warm-up (also sets the LDS attribute of the instantiation)
-        if (rc) break;
-        float ms_min = 1e30f;
-        for (int rep = 0; rep < 3 && !rc; ++rep) {
-            (void)hipEventRecord(e0, stream);
-            rc = run();
-            (void)hipEventRecord(e1, stream);
-            if (hipEventSynchronize(e1) != hipSuccess) rc = DENET_ERR_ARG;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            if (ms < ms_min) ms_min = ms;
-        }
-        if (rc) break;
-        if (ms_min < best_ms) {
-            best_ms = ms_min;
-            best = c;
-        }
-    }
-    t_try = TuneVal{-1, 0, 0};
-    g_prof_on = prof_was_on;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    TuneVal best;
+    const int rc = time_candidates("conv_tune", cand, stream, run, &best);
     if (rc) return rc;
     g_tuned[key] = best;
     return run();                                    // leave the result of the chosen configuration in `out`
@@ -1370,21 +1413,39 @@ extern "C" int denet_conv_last_config(int* mode, int* bm, int* bn, int* nbuf, in
     return DENET_OK;
 }
 
+static bool stem_ok(int pass, const Geom& g) {
+    return denet_conv_stem_ok(pass, g.N, g.H, g.W, g.C, g.K, g.R, g.S, g.S_real, g.stride, g.pad, g.OH, g.OW) != 0;
+}
+
+// sums_of (with stats): the column sums of the epilogue become a batch norm's backward reductions (denet_conv_dgrad_1x1t)
+static int conv_fwd_impl(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, double* stats,
+                         const Geom& g, hipStream_t stream, const denet_bn_link* sums_of = nullptr) {
+    int rc = check_geom(g);
+    if (rc) return rc;
+    DENET_CHECK_ARG(x && w && y, "conv_fwd: null pointer");
+    if (!add && !stats && stem_ok(0, g))
+        return denet_conv_stem_fwd_act(x, 0, w, bias, y, relu, nullptr, 0, nullptr, g.N, g.H, g.W, stream);
+    IgemmParams p = conv_params(g);
+    p.act = x; p.wgt = w; p.out = y; p.bias = bias; p.add = add; p.relu = relu ? 1 : 0; p.stats = stats;
+    if (sums_of && stats) set_bn_sums(p, *sums_of);
+    p.act_bytes = (unsigned)((size_t)g.N * g.H * g.W * g.C * 4); p.wgt_bytes = (unsigned)((size_t)g.K * g.R * g.S * g.C * 4);
+    p.M = g.N * g.OH * g.OW; p.NC = g.K; p.ksteps = g.R * g.S * g.C / BK; p.steps_per_split = p.ksteps;
+    p.npix = p.M;
+    p.div_row_hw.init(g.OH * g.OW); p.div_row_w.init(g.OW);
+    return launch_plan<MODE_FWD>(p, plan_fwd(g), stream);
+}
+
 extern "C" int denet_conv_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int N,
                               int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
                               int OW, hipStream_t stream) {
     return denet_conv_fwd_act(x, w, bias, add, y, 0, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW, stream);
 }
 
-static int conv_fwd_impl(const float* x, const float* w, const float* bias, const float* add, float* y, int relu,
-                         double* stats, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad,
-                         int OH, int OW, hipStream_t stream, const denet_bn_link* sums_of = nullptr);
-
 // forward convolution with an activation in the epilogue: y = act(conv(x, w) + bias + add), relu != 0: max(., 0)
 extern "C" int denet_conv_fwd_act(const float* x, const float* w, const float* bias, const float* add, float* y, int relu,
                                   int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
                                   int OW, hipStream_t stream) {
-    return conv_fwd_impl(x, w, bias, add, y, relu, nullptr, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW, stream);
+    return conv_fwd_impl(x, w, bias, add, y, relu, nullptr, Geom{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW}, stream);
 }
 
 // the same, and the epilogue also emits the per-channel sums of y for the batch norm that follows (batch_norm.py:50-53;
@@ -1394,69 +1455,41 @@ extern "C" int denet_conv_fwd_stats(const float* x, const float* w, const float*
                                     double* stats_partial, size_t stats_bytes, int* stats_rows, int N, int H, int W, int C,
                                     int K, int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream) {
     DENET_CHECK_ARG(stats_partial && stats_rows, "conv_fwd_stats: null pointer");
-    if (!add && denet_conv_stem_ok(0, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW))
-        return denet_conv_stem_fwd(x, w, bias, y, stats_partial, stats_bytes, stats_rows, N, H, W, stream);
+    const Geom g{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW};
+    if (!add && stem_ok(0, g)) return denet_conv_stem_fwd(x, w, bias, y, stats_partial, stats_bytes, stats_rows, N, H, W, stream);
     const long rows = ((long)N * OH * OW + 127) / 128;
     DENET_CHECK_ARG(stats_bytes >= (size_t)rows * 2 * K * sizeof(double), "conv_fwd_stats: statistics buffer too small");
     *stats_rows = (int)rows;
-    return conv_fwd_impl(x, w, bias, add, y, 0, stats_partial, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW, stream);
+    return conv_fwd_impl(x, w, bias, add, y, 0, stats_partial, g, stream);
 }
 
-static int conv_fwd_impl(const float* x, const float* w, const float* bias, const float* add, float* y, int relu,
-                         double* stats, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad,
-                         int OH, int OW, hipStream_t stream, const denet_bn_link* sums_of) {
-    int rc = check_geom(N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
-    if (rc) return rc;
-    DENET_CHECK_ARG(x && w && y, "conv_fwd: null pointer");
-    if (!add && !stats && denet_conv_stem_ok(0, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW))
-        return denet_conv_stem_fwd_act(x, 0, w, bias, y, relu, nullptr, 0, nullptr, N, H, W, stream);
-    IgemmParams p = {};
-    p.act = x; p.wgt = w; p.out = y; p.bias = bias; p.add = add; p.relu = relu ? 1 : 0; p.stats = stats;
-    if (sums_of && stats) {          // the column sums of the epilogue become a batch norm's backward reductions (denet_conv_dgrad_1x1t)
-        p.bs_x = sums_of->x; p.bs_y = sums_of->relu ? sums_of->y : nullptr; p.bs_gamma = sums_of->gamma; p.bs_beta = sums_of->beta;
-        p.bs_mean = sums_of->mean; p.bs_invstd = sums_of->invstd; p.bs_relu = sums_of->relu;
-    }
-    p.N = N; p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.K = K;
-    p.R = R; p.S = S; p.S_real = S_real; p.stride = stride; p.sshift = ilog2_exact(stride); p.pad = pad;
-    p.act_bytes = (unsigned)((size_t)N * H * W * C * 4); p.wgt_bytes = (unsigned)((size_t)K * R * S * C * 4);
-    p.M = N * OH * OW; p.NC = K; p.ksteps = R * S * C / BK; p.steps_per_split = p.ksteps;
-    p.npix = p.M;
-    p.div_row_hw.init(OH * OW); p.div_row_w.init(OW);
-    {
-        const long tm = ceil_div(p.M, 128);
-        const long nb[2] = {tm * ceil_div(K, 128), tm * ceil_div(K, 64)};
-        const double area[2] = {128.0 * 128.0, 128.0 * 64.0}, eff[2] = {1.0, 0.85};
-        // measured (tools/bench_conv.py): the pipelined 2-buffer loop wins on forward once the reduction has >= 24
-        // chunks (+4...14 %); shorter reductions (stem, 64-channel 3x3, 1x1 on 128 channels) amortise its longer
-        // prologue badly and run faster on the single-buffer loop at 3-4 workgroups per CU
-        const int want = (p.ksteps >= 24) ? 2 : 1;
-        Choice c = (K >= 128) ? choose_launch(nb, area, eff, 2, want) : choose_launch(nb + 1, area + 1, eff + 1, 1, want);
-        int tile = (K >= 128) ? c.tile : 1;
-        TuneVal tv;
-        if (tuned_choice(tune_key(MODE_FWD, N, H, W, C, K, R, S, S_real, stride, pad), &tv)) {
-            tile = (K >= 128) ? tv.tile : 1;
-            c.nbuf = tv.nbuf;
-        }
-        p.tiles_m = (int)tm;
-        if (tile == 0) {
-            p.tiles_n = ceil_div(K, 128);
-            take_final(p, 128, 1);
-            return LAUNCH_NBUF(MODE_FWD, 128, 128, c.nbuf, p, 1, stream);
-        }
-        p.tiles_n = ceil_div(K, 64);
-        take_final(p, 64, 1);
-        return LAUNCH_NBUF(MODE_FWD, 128, 64, c.nbuf, p, 1, stream);
-    }
-}
-
+// both data gradients; transposed: w is wt [R][S][C][K] (MODE_DGRAD_T)
 static int conv_dgrad_impl(const float* dy, const float* w, const float* add, float* dx, const denet_bn_link* sums_of,
-                           double* stats, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
-                           int OW, hipStream_t stream, bool transposed = false);
+                           double* stats, const Geom& g, hipStream_t stream, bool transposed) {
+    int rc = check_geom(g);
+    if (rc) return rc;
+    DENET_CHECK_ARG(dy && w && dx, "conv_dgrad: null pointer");
+    DENET_CHECK_ARG(g.C >= 32, "conv_dgrad: C < 32 not supported (first layer needs no data gradient)");
+    DENET_CHECK_ARG(g.H % g.stride == 0 && g.W % g.stride == 0, "conv_dgrad: H, W must be multiples of the stride");
+    IgemmParams p = conv_params(g);
+    p.act = dy; p.wgt = w; p.out = dx; p.add = add;
+    if (sums_of && stats) {
+        p.stats = stats;
+        set_bn_sums(p, *sums_of);
+    }
+    p.act_bytes = (unsigned)((size_t)g.N * g.OH * g.OW * g.K * 4); p.wgt_bytes = (unsigned)((size_t)g.K * g.R * g.S * g.C * 4);
+    p.Hc = g.H / g.stride; p.Wc = g.W / g.stride;
+    p.M = g.N * p.Hc * p.Wc; p.NC = g.C; p.ksteps = g.R * g.S * g.K / BK; p.steps_per_split = p.ksteps;
+    p.npix = g.N * g.OH * g.OW;
+    p.div_row_hw.init(p.Hc * p.Wc); p.div_row_w.init(p.Wc);
+    const IgemmPlan plan = plan_dgrad(g, transposed);
+    return transposed ? launch_plan<MODE_DGRAD_T>(p, plan, stream) : launch_plan<MODE_DGRAD>(p, plan, stream);
+}
 
 extern "C" int denet_conv_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W,
                                 int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW,
                                 hipStream_t stream) {
-    return conv_dgrad_impl(dy, w, add, dx, nullptr, nullptr, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW, stream);
+    return conv_dgrad_impl(dy, w, add, dx, nullptr, nullptr, Geom{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW}, stream, false);
 }
 
 // denet_conv_dgrad of a layer whose dx is the gradient of the OUTPUT of the batch norm `sums_of` (see
@@ -1466,15 +1499,11 @@ extern "C" int denet_conv_dgrad(const float* dy, const float* w, const float* ad
 extern "C" int denet_conv_dgrad_sums(const float* dy, const float* w, const float* add, float* dx, const denet_bn_link* sums_of,
                                      double* stats_partial, size_t stats_bytes, int* stats_rows, int N, int H, int W, int C, int K,
                                      int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream) {
-    DENET_CHECK_ARG(sums_of && stats_partial && stats_rows, "conv_dgrad_sums: null pointer");
-    DENET_CHECK_ARG(sums_of->x && sums_of->mean && sums_of->invstd && (!sums_of->relu || sums_of->y || (sums_of->gamma && sums_of->beta)),
-                    "conv_dgrad_sums: incomplete batch-norm description");
-    const bool geom = stride >= 1 && H % stride == 0 && W % stride == 0;
-    const long rows = geom ? (long)stride * stride * (((long)N * (H / stride) * (W / stride) + 127) / 128) : 0;
-    const bool ok = geom && stats_bytes >= (size_t)rows * 2 * C * sizeof(double);
-    *stats_rows = ok ? (int)rows : 0;
-    return conv_dgrad_impl(dy, w, add, dx, ok ? sums_of : nullptr, ok ? stats_partial : nullptr, N, H, W, C, K, R, S, S_real, stride,
-                           pad, OH, OW, stream);
+    bool ok = false;
+    const int rc = sums_request("conv_dgrad_sums", sums_of, stats_partial, stats_bytes, stats_rows, N, H, W, C, stride, &ok);
+    if (rc) return rc;
+    return conv_dgrad_impl(dy, w, add, dx, ok ? sums_of : nullptr, ok ? stats_partial : nullptr,
+                           Geom{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW}, stream, false);
 }
 
 // denet_conv_dgrad / denet_conv_dgrad_sums with the filter given transposed: wt [R][S][C][K] = denet_transpose_f32 of w [K][R*S*C]
@@ -1486,103 +1515,30 @@ extern "C" int denet_conv_dgrad_t(const float* dy, const float* wt, const float*
                                   int R, int S, int S_real, int stride, int pad, int OH, int OW, hipStream_t stream) {
     bool ok = false;
     if (sums_of) {
-        DENET_CHECK_ARG(stats_partial && stats_rows, "conv_dgrad_t: null pointer");
-        DENET_CHECK_ARG(sums_of->x && sums_of->mean && sums_of->invstd && (!sums_of->relu || sums_of->y || (sums_of->gamma && sums_of->beta)),
-                        "conv_dgrad_t: incomplete batch-norm description");
-        const bool geom = stride >= 1 && H % stride == 0 && W % stride == 0;
-        const long rows = geom ? (long)stride * stride * (((long)N * (H / stride) * (W / stride) + 127) / 128) : 0;
-        ok = geom && stats_bytes >= (size_t)rows * 2 * C * sizeof(double);
-        *stats_rows = ok ? (int)rows : 0;
+        const int rc = sums_request("conv_dgrad_t", sums_of, stats_partial, stats_bytes, stats_rows, N, H, W, C, stride, &ok);
+        if (rc) return rc;
     }
-    return conv_dgrad_impl(dy, wt, add, dx, ok ? sums_of : nullptr, ok ? stats_partial : nullptr, N, H, W, C, K, R, S, S_real, stride,
-                           pad, OH, OW, stream, true);
+    return conv_dgrad_impl(dy, wt, add, dx, ok ? sums_of : nullptr, ok ? stats_partial : nullptr,
+                           Geom{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW}, stream, true);
 }
 
 // the data gradient of a 1x1 stride-1 convolution as a FORWARD product over the transposed filter wt [C][K]
 // (dx[pix][c] = sum_k dy[pix][k] wt[c][k]): the forward loop reads both operands reduction-contiguous and runs the pipelined
 // 128 x 128 tile (the head layers: 118 -> 137, 100 -> 124 TFLOP/s against the k-major filter reads of the data-gradient mode),
 // same products in the same order - bit-identical to denet_conv_dgrad. sums_of / stats_partial as in denet_conv_dgrad_sums
-// (both null: no sums), rows = ceil(N*H*W / 128).
+// (both null: no sums), rows = ceil(N*H*W / 128): one parity class.
 extern "C" int denet_conv_dgrad_1x1t(const float* dy, const float* wt, const float* add, float* dx, const denet_bn_link* sums_of,
                                      double* stats_partial, size_t stats_bytes, int* stats_rows, int N, int H, int W, int C, int K,
                                      hipStream_t stream) {
     DENET_CHECK_ARG(dy && wt && dx, "conv_dgrad_1x1t: null pointer");
     bool ok = false;
     if (sums_of) {
-        DENET_CHECK_ARG(stats_partial && stats_rows, "conv_dgrad_1x1t: null pointer");
-        DENET_CHECK_ARG(sums_of->x && sums_of->mean && sums_of->invstd && (!sums_of->relu || sums_of->y || (sums_of->gamma && sums_of->beta)),
-                        "conv_dgrad_1x1t: incomplete batch-norm description");
-        const long rows = ((long)N * H * W + 127) / 128;
-        ok = stats_bytes >= (size_t)rows * 2 * C * sizeof(double);
-        *stats_rows = ok ? (int)rows : 0;
+        const int rc = sums_request("conv_dgrad_1x1t", sums_of, stats_partial, stats_bytes, stats_rows, N, H, W, C, 1, &ok);
+        if (rc) return rc;
     }
-    return conv_fwd_impl(dy, wt, nullptr, add, dx, 0, ok ? stats_partial : nullptr, N, H, W, K, C, 1, 1, 1, 1, 0, H, W, stream,
-                         ok ? sums_of : nullptr);
-}
-
-static int conv_dgrad_impl(const float* dy, const float* w, const float* add, float* dx, const denet_bn_link* sums_of,
-                           double* stats, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
-                           int OW, hipStream_t stream, bool transposed) {
-    int rc = check_geom(N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
-    if (rc) return rc;
-    DENET_CHECK_ARG(dy && w && dx, "conv_dgrad: null pointer");
-    DENET_CHECK_ARG(C >= 32, "conv_dgrad: C < 32 not supported (first layer needs no data gradient)");
-    IgemmParams p = {};
-    p.act = dy; p.wgt = w; p.out = dx; p.bias = nullptr; p.add = add;
-    if (sums_of && stats) {
-        p.stats = stats;
-        p.bs_x = sums_of->x; p.bs_y = sums_of->relu ? sums_of->y : nullptr; p.bs_gamma = sums_of->gamma; p.bs_beta = sums_of->beta;
-        p.bs_mean = sums_of->mean; p.bs_invstd = sums_of->invstd; p.bs_relu = sums_of->relu;
-    }
-    p.N = N; p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.K = K;
-    p.R = R; p.S = S; p.S_real = S_real; p.stride = stride; p.sshift = ilog2_exact(stride); p.pad = pad;
-    DENET_CHECK_ARG(H % stride == 0 && W % stride == 0, "conv_dgrad: H, W must be multiples of the stride");
-    p.act_bytes = (unsigned)((size_t)N * OH * OW * K * 4); p.wgt_bytes = (unsigned)((size_t)K * R * S * C * 4);
-    const int classes = stride * stride;
-    p.Hc = H / stride; p.Wc = W / stride;
-    p.M = N * p.Hc * p.Wc; p.NC = C; p.ksteps = R * S * K / BK; p.steps_per_split = p.ksteps;
-    p.npix = N * OH * OW;
-    p.div_row_hw.init(p.Hc * p.Wc); p.div_row_w.init(p.Wc);
-    {
-        const long tm = ceil_div(p.M, 128);
-        const long nb[2] = {tm * ceil_div(C, 128) * classes, tm * ceil_div(C, 64) * classes};
-        const double area[2] = {128.0 * 128.0, 128.0 * 64.0}, eff[2] = {1.0, 0.85};
-        // dgrad / wgrad read K-outer LDS tiles (4x the fragment-read instructions): the single-buffer loop at 3-4
-        // workgroups per CU measured faster than the pipelined one on every DeNet-34 layer but two (within 3 %)
-        Choice c = (C >= 128) ? choose_launch(nb, area, eff, 2, 1) : choose_launch(nb + 1, area + 1, eff + 1, 1, 1);
-        int tile = (C >= 128) ? c.tile : 1;
-        TuneVal tv;
-        if (tuned_choice(tune_key(MODE_DGRAD, N, H, W, C, K, R, S, S_real, stride, pad), &tv)) {
-            tile = (C >= 128) ? tv.tile : 1;
-            c.nbuf = tv.nbuf;
-        }
-        p.tiles_m = (int)tm;
-        if (transposed) {
-            // w is wt [R][S][C][K] (MODE_DGRAD_T): both operands reduction-contiguous, as in the forward pass - whose loop choice
-            // applies (the pipelined two-buffer loop from 24 chunks per parity class on); DENET_DGRAD_T_NBUF / _TILE: experiments
-            static const int env_nbuf = [] { const char* e = getenv("DENET_DGRAD_T_NBUF"); return e ? atoi(e) : 0; }();
-            static const int env_tile = [] { const char* e = getenv("DENET_DGRAD_T_TILE"); return e ? atoi(e) : 0; }();
-            const int per_class = p.ksteps / classes;
-            const int nbuf = env_nbuf ? env_nbuf : (per_class >= 24 ? 2 : 1);
-            const int wide = env_tile ? (env_tile == 1) : (C >= 128 && nbuf == 2 && nb[0] >= 512);
-            if (wide) {
-                p.tiles_n = ceil_div(C, 128);
-                take_final(p, 128, classes);
-                return LAUNCH_NBUF(MODE_DGRAD_T, 128, 128, nbuf, p, classes, stream);
-            }
-            p.tiles_n = ceil_div(C, 64);
-            take_final(p, 64, classes);
-            return LAUNCH_NBUF(MODE_DGRAD_T, 128, 64, nbuf, p, classes, stream);
-        }
-        if (tile == 0) {
-            p.tiles_n = ceil_div(C, 128);
-            take_final(p, 128, classes);
-            return LAUNCH_NBUF(MODE_DGRAD, 128, 128, c.nbuf, p, classes, stream);
-        }
-        p.tiles_n = ceil_div(C, 64);
-        take_final(p, 64, classes);
-        return LAUNCH_NBUF(MODE_DGRAD, 128, 64, c.nbuf, p, classes, stream);
-    }
+    // the forward pass with C and K swapped: also the key its plan looks a measured record up under (plan_dgrad_1x1t)
+    return conv_fwd_impl(dy, wt, nullptr, add, dx, 0, ok ? stats_partial : nullptr, swapped_1x1(Geom{N, H, W, C, K, 1, 1, 1, 1, 0, H, W}),
+                         stream, ok ? sums_of : nullptr);
 }
 
 extern "C" size_t denet_conv_wgrad_workspace_bytes(int N, int C, int K, int R, int S, int OH, int OW) {
@@ -1593,27 +1549,47 @@ extern "C" size_t denet_conv_wgrad_workspace_bytes(int N, int C, int K, int R, i
 extern "C" int denet_conv_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes,
                                 int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad,
                                 int OH, int OW, hipStream_t stream) {
-    int rc = check_geom(N, H, W, C, K, R, S, S_real, stride, pad, OH, OW);
+    const Geom g{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW};
+    int rc = check_geom(g);
     if (rc) return rc;
     DENET_CHECK_ARG(x && dy && dw, "conv_wgrad: null pointer");
-    if (workspace && workspace_bytes >= denet_conv_stem_wgrad_workspace_bytes() &&
-        denet_conv_stem_ok(1, N, H, W, C, K, R, S, S_real, stride, pad, OH, OW))
+    if (workspace && workspace_bytes >= denet_conv_stem_wgrad_workspace_bytes() && stem_ok(1, g))
         return denet_conv_stem_wgrad(x, dy, dw, workspace, workspace_bytes, N, H, W, stream);
-    IgemmParams p = {};
-    p.act = x; p.wgt = dy; p.bias = nullptr; p.add = nullptr;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.K = K;
-    p.R = R; p.S = S; p.S_real = S_real; p.stride = stride; p.sshift = ilog2_exact(stride); p.pad = pad;
+    IgemmParams p = conv_params(g);
+    p.act = x; p.wgt = dy;
     p.act_bytes = (unsigned)((size_t)N * H * W * C * 4); p.wgt_bytes = (unsigned)((size_t)N * OH * OW * K * 4);
     p.M = K; p.NC = R * S * C; p.npix = N * OH * OW;
-    {
-        static int v = -1;
-        if (v < 0) {
-            const char* e = getenv("DENET_WGRAD_SPLIT_SLOW");
-            v = e ? atoi(e) : 1;
-        }
-        p.wg_split_slow = v;
-    }
+    static const int split_slow = denet_env_int("DENET_WGRAD_SPLIT_SLOW", 1);
+    p.wg_split_slow = split_slow;
     p.div_row_hw.init(OH * OW); p.div_row_w.init(OW);
-    return wgrad_dispatch(p, K, dw, workspace, workspace_bytes, tune_key(MODE_WGRAD, N, H, W, C, K, R, S, S_real, stride, pad),
-                          stream);
+    return wgrad_dispatch(p, dw, workspace, workspace_bytes, tune_key(MODE_WGRAD, g), stream);
+}
+
+// The launch plan of one pass, computed and not launched (no device needed): what the entry point of that pass would run now.
+// Pass codes, geometry conventions and the meaning of *splits: include/denet_hip.h. 3 / 4 take the batched_geom() of the product.
+extern "C" int denet_conv_plan(int pass, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
+                               int OW, int batch, size_t workspace_bytes, int* bm, int* bn, int* nbuf, int* splits) {
+    DENET_CHECK_ARG(pass >= 0 && pass <= 6, "conv_plan: pass must be 0 ... 6");
+    DENET_CHECK_ARG(bm && bn && nbuf && splits, "conv_plan: null pointer");
+    const Geom g{N, H, W, C, K, R, S, S_real, stride, pad, OH, OW};
+    const int rc = check_geom(g);
+    if (rc) return rc;
+    IgemmPlan plan;
+    if (pass == 0) {
+        plan = plan_fwd(g);
+    } else if (pass == 1 || pass == 5) {
+        DENET_CHECK_ARG(C >= 32 && H % stride == 0 && W % stride == 0, "conv_plan: not a data-gradient geometry");
+        plan = plan_dgrad(g, pass == 5);
+    } else if (pass == 6) {
+        DENET_CHECK_ARG(R == 1 && S == 1 && S_real == 1 && stride == 1 && pad == 0 && C >= 32, "conv_plan: not a 1x1 stride-1 geometry");
+        plan = plan_dgrad_1x1t(g);
+    } else if (pass == 2) {
+        plan = plan_wgrad(tune_key(MODE_WGRAD, g), K, R * S * C, N * OH * OW, 1, workspace_bytes);
+    } else {
+        DENET_CHECK_ARG(batch > 0 && batch <= 65535 && N == 1 && H == 1 && R == 1 && S == 1 && stride == 1 && pad == 0 && C >= 32,
+                        "conv_plan: not a batched product");
+        plan = (pass == 3) ? plan_gemm_batched(batch, g) : plan_wgrad(batched_key(4, batch, g), K, C, W, batch, workspace_bytes);
+    }
+    *bm = plan.bm; *bn = plan.bn; *nbuf = plan.nbuf; *splits = plan.splits;
+    return DENET_OK;
 }

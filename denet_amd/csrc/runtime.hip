@@ -59,8 +59,7 @@ extern "C" int denet_bn_final_disarm(void) {
 static int g_bnf_mode = -1;
 static int bnf_mode() {
     if (g_bnf_mode < 0) {
-        const char* e = getenv("DENET_BN_FINAL_FOLD");
-        g_bnf_mode = e ? (atoi(e) & 3) : 0;
+        g_bnf_mode = denet_env_int("DENET_BN_FINAL_FOLD", 0) & 3;
     }
     return g_bnf_mode;
 }

@@ -433,11 +433,7 @@ int fill(StemParams& p, int N, int H, int W) {
 // DENET_STEM: bit 0 allows the forward kernel, bit 1 the filter gradient (default 3)
 extern "C" int denet_conv_stem_ok(int pass, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH,
                                   int OW) {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("DENET_STEM");
-        v = e ? atoi(e) : 3;
-    }
+    static const int v = denet_env_int("DENET_STEM", 3);
     return ((v >> (pass ? 1 : 0)) & 1) && C == 4 && K == 64 && R == 7 && S == 8 && S_real == 7 && stride == 2 && pad == 3 && H % 2 == 0 &&
            W % 2 == 0 && OH == H / 2 && OW == W / 2 && N > 0 && (long)N * H * W * 4 < (1L << 31);
 }
@@ -471,14 +467,11 @@ extern "C" int denet_conv_stem_fwd_act(const float* x, int x_nchw, const float* 
         *stats_rows = grid;
         p.stats = stats_partial;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)stem_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES);
-        if (e != hipSuccess) {
-            denet_set_error("conv_stem_fwd: hipFuncSetAttribute(%d B LDS): %s", F_LDS_BYTES, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_set[DENET_MAX_DEVICES] = {};
+    const hipError_t e = denet_allow_dynamic_lds((const void*)stem_fwd_kernel, F_LDS_BYTES, attr_set);
+    if (e != hipSuccess) {
+        denet_set_error("conv_stem_fwd: hipFuncSetAttribute(%d B LDS): %s", F_LDS_BYTES, hipGetErrorString(e));
+        return -(int)e;
     }
     const int prof = denet_prof_begin(12, 0, 0, 0, stream);
     hipLaunchKernelGGL(stem_fwd_kernel, dim3((unsigned)grid), dim3(NTH), F_LDS_BYTES, stream, p);
@@ -507,14 +500,11 @@ extern "C" int denet_conv_stem_wgrad_from(const float* x, int x_nchw, const floa
     const int grid = fill(p, N, H, W);
     DENET_CHECK_ARG(grid > 0, "conv_stem_wgrad: cannot query the device");
     DENET_CHECK_ARG(workspace_bytes >= (size_t)grid * PART * sizeof(float), "conv_stem_wgrad: workspace too small");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)stem_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES);
-        if (e != hipSuccess) {
-            denet_set_error("conv_stem_wgrad: hipFuncSetAttribute(%d B LDS): %s", G_LDS_BYTES, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_set[DENET_MAX_DEVICES] = {};
+    const hipError_t e = denet_allow_dynamic_lds((const void*)stem_wgrad_kernel, G_LDS_BYTES, attr_set);
+    if (e != hipSuccess) {
+        denet_set_error("conv_stem_wgrad: hipFuncSetAttribute(%d B LDS): %s", G_LDS_BYTES, hipGetErrorString(e));
+        return -(int)e;
     }
     const int prof = denet_prof_begin(13, 0, 0, 0, stream);
     hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)grid), dim3(NTH), G_LDS_BYTES, stream, p);

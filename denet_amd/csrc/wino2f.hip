@@ -720,16 +720,12 @@ extern "C" int denet_conv_wino2f_sums(const float* x, const float* u, const floa
             p.bs_mean = sums_of->mean; p.bs_invstd = sums_of->invstd; p.bs_relu = sums_of->relu;
         }
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wino2f_ws_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)wino2f_ws_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, S_LDS_BYTES);
-        if (e != hipSuccess) {
-            denet_set_error("conv_wino2f: hipFuncSetAttribute(%d B LDS): %s", S_LDS_BYTES, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_plain[DENET_MAX_DEVICES] = {}, attr_pref[DENET_MAX_DEVICES] = {};
+    hipError_t e = denet_allow_dynamic_lds((const void*)wino2f_ws_kernel<false>, S_LDS_BYTES, attr_plain);
+    if (e == hipSuccess) e = denet_allow_dynamic_lds((const void*)wino2f_ws_kernel<true>, S_LDS_BYTES, attr_pref);
+    if (e != hipSuccess) {
+        denet_set_error("conv_wino2f: hipFuncSetAttribute(%d B LDS): %s", S_LDS_BYTES, hipGetErrorString(e));
+        return -(int)e;
     }
     const int prof = denet_prof_begin(10, (p.add || p.bs_x) ? 1 : 0, 0, 0, stream);      // which instantiation runs
     // the variant that prefetches the output phase's operands only where there are any (it costs the plain pass 4 %)
@@ -778,14 +774,11 @@ extern "C" int denet_conv_wino2f_wgrad(const float* x, const float* dy, float* d
     p.by = (H + 15) / 16; p.bx = (W + 15) / 16;
     p.items = N * p.by * p.bx;
     p.x_bytes = (unsigned)((size_t)N * H * W * 64 * 4);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wino2f_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES);
-        if (e != hipSuccess) {
-            denet_set_error("conv_wino2f_wgrad: hipFuncSetAttribute(%d B LDS): %s", G_LDS_BYTES, hipGetErrorString(e));
-            return -(int)e;
-        }
-        attr_set = true;
+    static bool attr_set[DENET_MAX_DEVICES] = {};
+    const hipError_t e = denet_allow_dynamic_lds((const void*)wino2f_wgrad_kernel, G_LDS_BYTES, attr_set);
+    if (e != hipSuccess) {
+        denet_set_error("conv_wino2f_wgrad: hipFuncSetAttribute(%d B LDS): %s", G_LDS_BYTES, hipGetErrorString(e));
+        return -(int)e;
     }
     float* dU = p.part + (size_t)grid * 16 * 4096;
     const int prof = denet_prof_begin(11, 0, 0, 0, stream);

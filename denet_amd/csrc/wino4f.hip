@@ -487,8 +487,8 @@ int denet_wino4f_block(int tile, long T, int C, int K) {
     // V / U go through 32-bit buffer descriptors and the kernel steps through the components with a signed 32-bit byte offset
     // (d_sV reaches 36 * T * C * 4): a problem beyond that takes the un-fused path instead of failing in denet_wino4f_run
     if (36L * T * C * 4 >= (1L << 31) || 36L * K * C * 4 >= (1L << 31)) return 0;
-    static const int env_on = [] { const char* e = getenv("DENET_WINO4F"); return e ? atoi(e) : 1; }();
-    static const int env_tb = [] { const char* e = getenv("DENET_WINO4F_TB"); return e ? atoi(e) : 0; }();
+    static const int env_on = denet_env_int("DENET_WINO4F", 1);
+    static const int env_tb = denet_env_int("DENET_WINO4F_TB", 0);
     const int mode = g_w4_mode >= 0 ? g_w4_mode : (env_on ? env_tb : 0);
     if (g_w4_mode < 0 && !env_on) return 0;
     if (g_w4_mode == 0) return 0;

@@ -200,7 +200,7 @@ extern "C" int denet_conv_wino4g_mode(int mode) {
 static int g4_nbuf(int C, int K) { return 36L * (K / 128) * (C / 128) <= 72 ? 4 : 3; }
 int denet_wino4g_splits(int tile, long T, int C, int K) {
     if (tile != 4 || C % 128 != 0 || K % 128 != 0 || T < 64) return 0;
-    static const int env_on = [] { const char* e = getenv("DENET_WINO4G"); return e ? atoi(e) : 1; }();
+    static const int env_on = denet_env_int("DENET_WINO4G", 1);
     if (g_g4_mode == 0 || (g_g4_mode < 0 && !env_on)) return 0;
     if ((long)36 * T * (K > C ? K : C) * 4 >= 0x7FFFFFFFL) return 0;      // 32-bit byte offsets into the operands
     const long blocks = 36L * (K / 128) * (C / 128);

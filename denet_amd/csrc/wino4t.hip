@@ -580,7 +580,7 @@ extern "C" int denet_conv_wino4t_sums(const float* x, const float* u_packed, con
         return -(int)e;
     }
     // (experiments: DENET_W4T_LDS = LDS bytes requested per workgroup, e.g. 100000 leaves room for ONE workgroup per CU)
-    static const int lds_req = [] { const char* e = getenv("DENET_W4T_LDS"); const int v = e ? atoi(e) : 0; return v > T_LDS && v <= 163840 ? v : T_LDS; }();
+    static const int lds_req = [] { const int v = denet_env_int("DENET_W4T_LDS", 0); return v > T_LDS && v <= 163840 ? v : T_LDS; }();
     const int prof = denet_prof_begin(16, ep, 0, 0, stream);
     hipLaunchKernelGGL(fn, dim3((unsigned)(blocks * p.tiles_k)), dim3(256), lds_req, stream, p);
     denet_prof_end(prof, stream);

@@ -359,6 +359,21 @@ int denet_tune_export(int* records, int capacity);
 int denet_tune_import(const int* records, int count);
 int denet_tune_clear(void);
 int denet_conv_last_config(int* mode, int* bm, int* bn, int* nbuf, int* grid_y);
+/* the launch plan of one implicit-GEMM pass, computed and NOT launched (needs no device): the tile BM x BN, the loop structure
+ * (LDS buffers) and the splits that the pass's entry point would run now - given the measured records, a candidate under test
+ * and the DENET_* switches -, i.e. what denet_conv_last_config reports after that call.
+ *   pass 0 = denet_conv_fwd / _fwd_act / _fwd_stats      1 = denet_conv_dgrad / _dgrad_sums     2 = denet_conv_wgrad
+ *        3 = a batched component GEMM, 4 = a batched filter-gradient product of the denet_conv_wino_* passes
+ *            (0 - 4: the mode field of the tune records)
+ *        5 = denet_conv_dgrad_t                          6 = denet_conv_dgrad_1x1t
+ * The geometry is the one the entry point takes (6: R = S = S_real = stride = 1, pad = 0, OH = H, OW = W). 3 / 4: N = H = OH = 1,
+ * R = S = S_real = stride = 1, pad = 0, W = OW = the rows M of the product (4: its reduction length T), C = its reduction width
+ * Kc (4: its columns Cc), K = its columns Nc (4: its rows Kr), `batch` = the members (other passes ignore it).
+ * workspace_bytes: the split workspace of 2 / 4 (0: none; other passes ignore it). The geometries the stem kernels take over
+ * (csrc/stem.hip) are answered for the implicit-GEMM kernel all the same.
+ * *splits: 0 / 6: 1; 1 / 5: stride^2 parity classes; 2 / 4: split slices; 3: the members. */
+int denet_conv_plan(int pass, int N, int H, int W, int C, int K, int R, int S, int S_real, int stride, int pad, int OH, int OW,
+                    int batch, size_t workspace_bytes, int* bm, int* bn, int* nbuf, int* splits);
 /* live timing of the igemm kernel alone (bench.py roofline leg): denet_conv_profile(1) starts recording one HIP event
  * pair per convolution launch on the launch stream, (0) stops and frees; _read returns the duration of launch i and the
  * instantiation <mode,BM,BN,2,2,NBUF> it used (the name rocprofv3 --kernel-trace shows). denet_conv_profile(2) records the

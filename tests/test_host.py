@@ -833,7 +833,7 @@ def test_desc_grammar_matches_the_executed_reference_parser():
 
 
 def test_every_environment_switch_is_registered():
-    """denet_amd/switches.py lists every DENET_* environment switch the sources read (Python: os.environ.get, C++: getenv), with its
+    """denet_amd/switches.py lists every DENET_* environment switch the sources read (Python: os.environ.get, C++: denet_env_int / getenv), with its
     default - the one place that says what the product default is; bench.py reports the switches a run was taken with against it"""
     import re
     from denet_amd import switches
@@ -845,7 +845,7 @@ def test_every_environment_switch_is_registered():
                                                       if f.endswith((".py", ".hip", ".h")) and "native" not in d]
         for f in files:
             with open(f, errors="ignore") as fh:
-                found |= set(re.findall(r'(?:getenv\(|environ\.get\(|environ\[)"(DENET_[A-Z0-9_]+)"', fh.read()))
+                found |= set(re.findall(r'(?:getenv\(|denet_env_int\(|environ\.get\(|environ\[)"(DENET_[A-Z0-9_]+)"', fh.read()))
     missing = sorted(found - set(switches.SWITCHES))
     assert not missing, "switches read by the sources but not listed in denet_amd/switches.py: %s" % missing
     stale = sorted(k for k in switches.SWITCHES if k not in found)

@@ -891,6 +891,164 @@ def test_data_gradient_of_a_1x1_layer_over_the_transposed_filter(hip, case):
             assert torch.equal(a, b), mode
 
 
+class _TunedTable:
+    """the process's table of measured launch configurations, emptied for the test and put back afterwards"""
+
+    def __enter__(self):
+        import ctypes
+        from denet_amd import ops
+        self.L = ops._L()
+        self.n = self.L.denet_tune_export(None, 0)
+        self.saved = (ctypes.c_int * (14 * max(self.n, 1)))()
+        assert self.L.denet_tune_export(self.saved, self.n) == self.n
+        assert self.L.denet_tune_clear() == 0
+        return self.L
+
+    def __exit__(self, *exc):
+        assert self.L.denet_tune_clear() == 0
+        assert self.L.denet_tune_import(self.saved, self.n) == 0
+        assert self.L.denet_tune_export(None, 0) == self.n
+
+
+def _igemm_pass(L, code, g, t, ws_bytes):
+    """runs pass `code` (denet_conv_plan's codes) of geometry g on the tensors t through the C ABI; returns the output tensor"""
+    from denet_amd.ops import ptr, stream_ptr
+    N, H, W, C, K = g[:5]
+    if code == 0:
+        rc, out = L.denet_conv_fwd(ptr(t["x"]), ptr(t["w"]), None, None, ptr(t["y"]), *g, stream_ptr()), t["y"]
+    elif code == 1:
+        rc, out = L.denet_conv_dgrad(ptr(t["dy"]), ptr(t["w"]), None, ptr(t["dx"]), *g, stream_ptr()), t["dx"]
+    elif code == 5:
+        rc, out = L.denet_conv_dgrad_t(ptr(t["dy"]), ptr(t["wt"]), None, ptr(t["dx"]), None, None, 0, None, *g, stream_ptr()), t["dx"]
+    elif code == 6:
+        rc, out = L.denet_conv_dgrad_1x1t(ptr(t["dy"]), ptr(t["wt"]), None, ptr(t["dx"]), None, None, 0, None, N, H, W, C, K,
+                                          stream_ptr()), t["dx"]
+    else:
+        rc, out = L.denet_conv_wgrad(ptr(t["x"]), ptr(t["dy"]), ptr(t["dw"]), ptr(t["ws"]), ws_bytes, *g, stream_ptr()), t["dw"]
+    assert rc == 0, (code, g, rc, L.denet_last_error())
+    return out
+
+
+def _igemm_tensors(g, seed):
+    N, H, W, C, K, R, S, _, stride, pad, OH, OW = g
+    gen = torch.Generator().manual_seed(seed)
+    t = {"x": torch.randn(N, H, W, C, generator=gen).cuda(), "w": (torch.randn(K, R, S, C, generator=gen) * 0.1).cuda(),
+         "dy": torch.randn(N, OH, OW, K, generator=gen).cuda()}
+    t["wt"] = t["w"].reshape(K, R * S * C).t().contiguous()            # [R][S][C][K]
+    t["y"], t["dx"], t["dw"] = torch.empty_like(t["dy"]), torch.empty_like(t["x"]), torch.empty_like(t["w"])
+    t["ws"] = torch.empty(64 * t["w"].numel(), device="cuda")            # room for 64 split slices
+    return t
+
+
+@pytest.mark.parametrize("code,C,K,R,stride,pad", [
+    (0, 32, 160, 3, 1, 1), (1, 32, 160, 3, 1, 1), (5, 32, 160, 3, 1, 1), (2, 32, 160, 3, 1, 1), (6, 32, 160, 1, 1, 0),
+    (1, 160, 32, 3, 1, 1), (5, 160, 32, 3, 1, 1), (6, 160, 32, 1, 1, 0),            # the data gradients' columns are C
+    (1, 32, 160, 3, 2, 1), (5, 32, 160, 3, 2, 1), (1, 160, 32, 3, 2, 1), (5, 160, 32, 3, 2, 1),
+])
+@pytest.mark.parametrize("state", ["cleared", "committed"])
+def test_what_is_planned_is_what_runs(hip, code, C, K, R, stride, pad, state):
+    """denet_conv_plan against denet_conv_last_config of the launch itself, at batch 2, 16 x 16: 160 channels are two column
+    tiles of 128 (or three of 64), the last one padded; stride 2 runs four parity classes; the filter gradient has workspace for
+    more than one split slice. With the table of measured configurations empty and as the process loaded it."""
+    import ctypes
+    from denet_amd import ops
+    g = ops.conv_geom((2, 16, 16, C), (K, R, R, C), stride, pad)
+    t = _igemm_tensors(g, 3)
+    ws_bytes = t["ws"].numel() * 4
+
+    def check_once(L):
+        plan = [ctypes.c_int() for _ in range(4)]
+        assert L.denet_conv_plan(code, *g, 1, ws_bytes if code == 2 else 0, *[ctypes.byref(v) for v in plan]) == 0
+        _igemm_pass(L, code, g, t, ws_bytes)
+        ran = [ctypes.c_int() for _ in range(5)]
+        L.denet_conv_last_config(*[ctypes.byref(v) for v in ran])
+        assert [v.value for v in ran] == [{0: 0, 1: 1, 2: 2, 5: 3, 6: 0}[code]] + [v.value for v in plan]
+        return [v.value for v in plan]
+
+    if state == "cleared":
+        with _TunedTable() as L:
+            plan = check_once(L)
+    else:
+        ops._load_tuned_once()
+        plan = check_once(ops._L())
+    torch.cuda.synchronize()
+    assert plan[3] == (stride * stride if code in (1, 5) else 1) or code == 2
+    if code == 2:
+        assert plan[3] > 1, plan                      # 16 pixel chunks, 64 slices of workspace: the price loop splits
+
+
+@pytest.mark.parametrize("mode,C,K,ncand", [(0, 32, 160, 4), (1, 160, 32, 4), (2, 32, 160, 9)])
+def test_conv_tune_times_its_candidates_and_keeps_one(hip, mode, C, K, ncand):
+    """denet_conv_tune (the timing loop of csrc/igemm.hip) at batch 2, 16 x 16, 3x3: it stores one of its candidates, leaves the
+    pass's result in `out` - the bits of an untuned run for forward and data gradient, whose candidates sum in one order; the
+    filter gradient (another split-K grouping) within the tolerance of test_conv_fwd_dgrad_wgrad against float64 -, and a second
+    call measures nothing: one launch, the record as it was."""
+    import ctypes
+    from denet_amd import ops
+    from denet_amd.ops import ptr, stream_ptr
+    g = ops.conv_geom((2, 16, 16, C), (K, 3, 3, C), 1, 1)
+    t = _igemm_tensors(g, 5 + mode)
+    ws_bytes = t["ws"].numel() * 4
+    a, b, out = {0: ("x", "w", "y"), 1: ("dy", "w", "dx"), 2: ("x", "dy", "dw")}[mode]
+    cand = {(0, nb, r) for nb, rr in ((1, 6), (2, 3)) for r in range(1, rr + 1)} if mode == 2 else \
+        {(tl, nb, 0) for tl in (0, 1) for nb in (1, 2)}
+    assert len(cand) == ncand
+
+    def record(L):
+        v = [ctypes.c_int() for _ in range(3)]
+        rc = L.denet_conv_tuned(mode, *g[:10], *[ctypes.byref(x) for x in v])
+        return rc, tuple(x.value for x in v)
+
+    def tune(L):
+        return L.denet_conv_tune(mode, ptr(t[a]), ptr(t[b]), None, None, ptr(t[out]), ptr(t["ws"]), ws_bytes, *g, stream_ptr())
+
+    with _TunedTable() as L:
+        assert record(L)[0] == 1
+        plain = _igemm_pass(L, mode, g, t, ws_bytes).clone()
+        t[out].zero_()
+        assert tune(L) == 0, L.denet_last_error()
+        rc, rec = record(L)
+        assert rc == 0 and rec in cand, rec
+        tuned = t[out].clone()
+        t[out].zero_()
+        assert L.denet_conv_profile(2) == 0              # launch trace: which matrix kernels the second call starts
+        try:
+            assert tune(L) == 0
+            launches = L.denet_conv_profile_count()
+        finally:
+            L.denet_conv_profile(0)
+        assert launches == 1 and record(L) == (0, rec)
+        assert torch.equal(t[out], tuned)
+    if mode == 2:
+        x64, dy64 = t["x"].double().permute(0, 3, 1, 2), t["dy"].double().permute(0, 3, 1, 2)
+        ref = torch.nn.grad.conv2d_weight(x64, (K, C, 3, 3), dy64, stride=1, padding=1).permute(0, 2, 3, 1)
+        _close(tuned, ref.float())
+        _close(plain, ref.float())
+    else:
+        assert torch.equal(tuned, plain)
+
+
+def test_conv_wino_tune_leaves_a_record_per_batched_product(hip):
+    """denet_conv_wino_tune at F(2x2), batch 2, 8 x 8, 32 channels: the same timing loop over the batched component GEMM (mode 3,
+    one key for forward and data gradient at C = K) and the batched filter-gradient product (mode 4) of 16 members, 32 tiles"""
+    import ctypes
+    from denet_amd.ops import ptr, stream_ptr
+    N, H, W, C, K, tile = 2, 8, 8, 32, 32, 2
+    with _TunedTable() as L:
+        ws = torch.empty(L.denet_conv_wino_workspace_bytes(tile, N, H, W, C, K) // 4, device="cuda")
+        sws = torch.empty(64 * 16 * C * K, device="cuda")
+        key = (16, 1, N * (H // tile) * (W // tile), C, K, 1, 1, 1, 1, 0)
+        v = [ctypes.c_int() for _ in range(3)]
+        assert L.denet_conv_tuned(3, *key, *[ctypes.byref(x) for x in v]) == 1
+        assert L.denet_conv_wino_tune(ptr(ws), ws.numel() * 4, ptr(sws), sws.numel() * 4, tile, N, H, W, C, K, stream_ptr()) == 0, \
+            L.denet_last_error()
+        assert L.denet_tune_export(None, 0) == 2
+        assert L.denet_conv_tuned(3, *key, *[ctypes.byref(x) for x in v]) == 0
+        assert tuple(x.value for x in v) in {(1, 1, 0), (1, 2, 0)}                      # 32 columns: the 128 x 64 tile only
+        assert L.denet_conv_tuned(4, *key, *[ctypes.byref(x) for x in v]) == 0
+        assert tuple(x.value for x in v) in {(0, nb, r) for nb, rr in ((1, 6), (2, 3)) for r in range(1, rr + 1)}
+
+
 @pytest.mark.parametrize("shape", [(4, 16, 16, 64), (2, 8, 8, 1536), (3, 5, 7, 768), (2, 32, 32, 128)])
 @pytest.mark.parametrize("relu,res", [(False, False), (True, False), (True, True)])
 def test_bn_fwd_bwd(hip, shape, relu, res):
