@@ -2,7 +2,9 @@
 // description (reference: denet/layer/convolution.py:55-83,99-112, deconvolution.py:54-65; gradients: tensor.grad,
 // model_cnn.py:318). Filter R x S, stride (sh, sw), padding (ph, pw), output OH x OW given by the caller. The square kernels
 // of igemm.hip / winograd.hip take ONE stride and ONE pad; this file is the direct kernel of everything else and shares no
-// code path with them.
+// code path with them. The same text with the taps of a filter (dh, dw) apart is the dilated convolution of the `C.D[k, size,
+// stride, d]` / `C.DX[k, kh, kw, sh, sw, dh, dw]` tokens and the dilated residual blocks (conv_dil_kernel; this build's own
+// contract, DESIGN.md section 19: the reference has no dilation).
 //
 // Layout (HBM):   activations NHWC fp32, filters KRSC fp32 correlation taps (as igemm.hip).
 // Arithmetic:     v_mfma_f32_32x32x2_f32, exact fp32 FMA chain, accumulators in registers.
@@ -46,7 +48,11 @@ struct RectParams {
     FastDiv div_img;     // fwd / wgrad: OH*OW   dgrad: Hc*Wc
     FastDiv div_row;     // fwd / wgrad: OW      dgrad: Wc
     unsigned a_bytes, b_bytes;   // extents of a / b: lanes outside read 0 through the buffer descriptor
+    // dilation: tap (r, s) reads row r*dh, column s*dw of its window (read by the DIL instantiations only). 16 bits each: the pair
+    // fills the 4 bytes the struct ended in unused, so the kernel arguments of conv_rect_kernel lie where they lay without it
+    unsigned short dh, dw;
 };
+static_assert(sizeof(RectParams) == 192, "RectParams: the kernel-argument layout of conv_rect_kernel is part of its device code");
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 constexpr int OOB_OFFSET = (int)0xF0000000u;   // beyond every extent check_rect admits
@@ -55,8 +61,12 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, int elem_of
     return __builtin_bit_cast(f32x4, v);
 }
 
-template <int PASS, int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
+// The one text of all three passes. DIL = false: the taps of a filter are neighbours (conv_rect_kernel); DIL = true: they lie
+// (dh, dw) apart (conv_dil_kernel). A dilated axis has stride 1 (check_rect), so the data gradient's classes are those of the
+// strides alone and its tap walk steps by the dilation. Every dilated term sits behind DIL.
+template <bool DIL, int PASS, int BM, int BN, int WM, int WN>
+__device__ __forceinline__ void conv_rect_body(const RectParams p) {
+    const int dh = DIL ? p.dh : 1, dw = DIL ? p.dw : 1;
     constexpr bool A_KIN = (PASS != PASS_WGRAD);
     constexpr bool B_KIN = (PASS == PASS_FWD);
     constexpr int TM = BM / (32 * WM);
@@ -123,7 +133,9 @@ __global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
             const int m = m0 + row8 + 32 * i;
-            a_y[i] = -(p.R + 1); a_x[i] = 0; a_off[i] = 0;      // a row that is none: every tap lies above the image
+            // a row that is none: every tap lies above the image. Dilated, -(R + 1) + r * dh could come back inside it: the row sits
+            // at -(ke_h + 1), ke_h = (R - 1) * dh + 1, and its last tap at -2
+            a_y[i] = DIL ? -((p.R - 1) * dh + 2) : -(p.R + 1); a_x[i] = 0; a_off[i] = 0;
             if (m < p.M) {
                 const uint32_t n = p.div_img.div(m);
                 const uint32_t rem = m - n * (p.OH * p.OW);
@@ -189,11 +201,12 @@ __global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
 
     auto load_chunk = [&]() {
         if (PASS == PASS_FWD) {
-            const int u_off = (cur_r * p.W + cur_s) * p.C + cur_c;
+            const int tap_y = DIL ? cur_r * dh : cur_r, tap_x = DIL ? cur_s * dw : cur_s;
+            const int u_off = (tap_y * p.W + tap_x) * p.C + cur_c;
             const bool tap_ok = cur_s + qs < p.S_real;
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
-                const bool ok = tap_ok && ((unsigned)(a_y[i] + cur_r) < (unsigned)p.H) && ((unsigned)(a_x[i] + cur_s) < (unsigned)p.W);
+                const bool ok = tap_ok && ((unsigned)(a_y[i] + tap_y) < (unsigned)p.H) && ((unsigned)(a_x[i] + tap_x) < (unsigned)p.W);
                 ra[i] = buf_load4(r_a, a_off[i] + u_off, ok);
             }
 #pragma unroll
@@ -211,7 +224,7 @@ __global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
         } else if (PASS == PASS_DGRAD) {
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
-                const int oy = a_y[i] - cur_r, ox = a_x[i] - cur_s;
+                const int oy = a_y[i] - (DIL ? cur_r * dh : cur_r), ox = a_x[i] - (DIL ? cur_s * dw : cur_s);
                 const bool ok = ((unsigned)oy < (unsigned)p.OH) && ((unsigned)ox < (unsigned)p.OW);
                 ra[i] = buf_load4(r_a, a_off[i] + (oy * p.OW + ox) * p.K + cur_c, ok);
             }
@@ -237,8 +250,8 @@ __global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
                 const uint32_t rem = pix - n * (p.OH * p.OW);
                 const uint32_t oy = p.div_row.div(rem);
                 const uint32_t ox = rem - oy * p.OW;
-                const int iy = (int)oy * p.sh - p.ph + wg_r;
-                const int ix = (int)ox * p.sw - p.pw + wg_s;
+                const int iy = (int)oy * p.sh - p.ph + (DIL ? wg_r * dh : wg_r);
+                const int ix = (int)ox * p.sw - p.pw + (DIL ? wg_s * dw : wg_s);
                 const bool ok = wg_colok && (pix < p.npix) && ((unsigned)iy < (unsigned)p.H) && ((unsigned)ix < (unsigned)p.W);
                 rb[i] = buf_load4(r_b, (((int)n * p.H + iy) * p.W + ix) * p.C + wg_c, ok);
             }
@@ -355,6 +368,17 @@ __global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
     }
 }
 
+template <int PASS, int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
+    conv_rect_body<false, PASS, BM, BN, WM, WN>(p);
+}
+
+// the same passes with the taps (dh, dw) apart: the `C.D[...]` / `C.DX[...]` layers and the dilated residual blocks
+template <int PASS, int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void conv_dil_kernel(const RectParams p) {
+    conv_rect_body<true, PASS, BM, BN, WM, WN>(p);
+}
+
 // dw = the slices added in slice order (one float4 column per thread)
 __global__ __launch_bounds__(256) void conv_rect_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out, long n4,
                                                                int splits) {
@@ -366,13 +390,19 @@ __global__ __launch_bounds__(256) void conv_rect_reduce_kernel(const float* __re
     ((f32x4*)out)[col] = s;
 }
 
-int check_rect(const char* who, int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
-               int OW) {
+int check_rect(const char* who, int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh,
+               int dw, int OH, int OW) {
     DENET_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && K > 0 && R > 0 && S > 0, "%s: non-positive dimension", who);
     DENET_CHECK_ARG(S_real > 0 && S_real <= S, "%s: S_real (%d) out of range", who, S_real);
     DENET_CHECK_ARG(ilog2_exact(sh) >= 0, "%s: row stride sh must be a power of two (got %d)", who, sh);
     DENET_CHECK_ARG(ilog2_exact(sw) >= 0, "%s: column stride sw must be a power of two (got %d)", who, sw);
     DENET_CHECK_ARG(ph >= 0 && pw >= 0, "%s: negative padding (ph %d, pw %d)", who, ph, pw);
+    DENET_CHECK_ARG(dh >= 1, "%s: row dilation dh must be at least 1 (got %d)", who, dh);
+    DENET_CHECK_ARG(dw >= 1, "%s: column dilation dw must be at least 1 (got %d)", who, dw);
+    DENET_CHECK_ARG(dh <= 0xFFFF && dw <= 0xFFFF, "%s: dilation (dh %d, dw %d) beyond 65535", who, dh, dw);
+    // a dilated axis has stride 1: the data gradient's classes of input pixels are those of the strides alone
+    DENET_CHECK_ARG(dh == 1 || sh == 1, "%s: row stride sh must be 1 on a dilated axis (sh %d, dh %d)", who, sh, dh);
+    DENET_CHECK_ARG(dw == 1 || sw == 1, "%s: column stride sw must be 1 on a dilated axis (sw %d, dw %d)", who, sw, dw);
     DENET_CHECK_ARG(K % 32 == 0, "%s: physical K (%d) must be a multiple of 32", who, K);
     if (C >= 32) {
         DENET_CHECK_ARG(C % 32 == 0, "%s: physical C (%d) must be a multiple of 32", who, C);
@@ -381,8 +411,11 @@ int check_rect(const char* who, int N, int H, int W, int C, int K, int R, int S,
         DENET_CHECK_ARG(C == 4 || C == 8 || C == 16, "%s: small C must be 4, 8 or 16 (got %d)", who, C);
         DENET_CHECK_ARG((S * C) % 32 == 0, "%s: S*C (%d) must be a multiple of 32 for small C", who, S * C);
     }
-    DENET_CHECK_ARG(H + 2 * ph >= R && OH > 0 && (H + 2 * ph - R) / sh + 1 >= OH, "%s: OH=%d inconsistent", who, OH);
-    DENET_CHECK_ARG(W + 2 * pw >= S_real && OW > 0 && (W + 2 * pw - S_real) / sw + 1 >= OW, "%s: OW=%d inconsistent", who, OW);
+    // (the small-C path packs several taps of a filter row into one chunk: neighbours only)
+    DENET_CHECK_ARG((dh == 1 && dw == 1) || C % 32 == 0, "%s: a dilated filter needs physical C (%d) to be a multiple of 32", who, C);
+    const long keh = (long)(R - 1) * dh + 1, kew = (long)(S_real - 1) * dw + 1;      // effective extents
+    DENET_CHECK_ARG(H + 2 * ph >= keh && OH > 0 && (H + 2 * ph - keh) / sh + 1 >= OH, "%s: OH=%d inconsistent", who, OH);
+    DENET_CHECK_ARG(W + 2 * pw >= kew && OW > 0 && (W + 2 * pw - kew) / sw + 1 >= OW, "%s: OW=%d inconsistent", who, OW);
     // 32-bit buffer descriptors (byte offsets); 0xF0000000 marks a lane that reads nothing. The padded class grid of the
     // data gradient (ceil(H/sh)*sh x ceil(W/sw)*sw) is indexed with 32-bit integers as well
     DENET_CHECK_ARG((long)N * (H + sh) * (W + sw) * C * 4 < 0xF0000000L && (long)N * OH * OW * K * 4 < 0xF0000000L &&
@@ -391,43 +424,46 @@ int check_rect(const char* who, int N, int H, int W, int C, int K, int R, int S,
     return DENET_OK;
 }
 
-RectParams make_params(int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW) {
+RectParams make_params(int N, int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw,
+                       int OH, int OW) {
     RectParams p = {};
     p.N = N; p.H = H; p.W = W; p.C = C; p.OH = OH; p.OW = OW; p.K = K; p.R = R; p.S = S; p.S_real = S_real;
     p.sh = sh; p.sw = sw; p.shs = ilog2_exact(sh); p.sws = ilog2_exact(sw); p.ph = ph; p.pw = pw;
+    p.dh = (unsigned short)dh; p.dw = (unsigned short)dw;
     p.npix = N * OH * OW;
     return p;
 }
 
-template <int PASS, int BM, int BN, int WM, int WN>
+template <bool DIL, int PASS, int BM, int BN, int WM, int WN>
 int launch_rect(RectParams& p, unsigned grid_y, hipStream_t stream) {
     constexpr bool A_KIN = (PASS != PASS_WGRAD);
     constexpr bool B_KIN = (PASS == PASS_FWD);
     constexpr int SZA = A_KIN ? BM * LDK : BK * (BM + 4);
     constexpr int SZB = B_KIN ? BN * LDK : BK * (BN + 4);
     constexpr size_t lds = 2 * (size_t)(SZA + SZB) * sizeof(float);
+    void (*const kernel)(const RectParams) = DIL ? conv_dil_kernel<PASS, BM, BN, WM, WN> : conv_rect_kernel<PASS, BM, BN, WM, WN>;
     static bool attr_set[DENET_MAX_DEVICES] = {};
-    const hipError_t e = denet_allow_dynamic_lds((const void*)conv_rect_kernel<PASS, BM, BN, WM, WN>, (int)lds, attr_set);
+    const hipError_t e = denet_allow_dynamic_lds((const void*)kernel, (int)lds, attr_set);
     if (e != hipSuccess) {
         denet_set_error("conv_rect: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
         return -(int)e;
     }
     p.tiles_m = ceil_div(p.M, BM);
     p.tiles_n = ceil_div(p.NC, BN);
-    const int prof = denet_prof_begin(20, PASS, BM, BN, stream);       // ops.kernel_symbol: conv_rect_kernel<PASS, BM, BN>
-    hipLaunchKernelGGL((conv_rect_kernel<PASS, BM, BN, WM, WN>), dim3((unsigned)(p.tiles_m * p.tiles_n), grid_y, 1), dim3(256), lds,
-                       stream, p);
+    // ops.kernel_symbol: 20 = conv_rect_kernel<PASS, BM, BN>, 25 = conv_dil_kernel<PASS, BM, BN>
+    const int prof = denet_prof_begin(DIL ? 25 : 20, PASS, BM, BN, stream);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(p.tiles_m * p.tiles_n), grid_y, 1), dim3(256), lds, stream, p);
     denet_prof_end(prof, stream);
-    DENET_CHECK_LAUNCH("conv_rect");
+    DENET_CHECK_LAUNCH(DIL ? "conv_dil" : "conv_rect");
     return DENET_OK;
 }
 
 // rows of 128 pixels against 128 / 64 / 32 output columns (fwd, dgrad)
-template <int PASS>
+template <bool DIL, int PASS>
 int launch_by_cols(RectParams& p, unsigned grid_y, hipStream_t stream) {
-    if (p.NC >= 96) return launch_rect<PASS, 128, 128, 2, 2>(p, grid_y, stream);
-    if (p.NC >= 64) return launch_rect<PASS, 128, 64, 2, 2>(p, grid_y, stream);
-    return launch_rect<PASS, 128, 32, 4, 1>(p, grid_y, stream);
+    if (p.NC >= 96) return launch_rect<DIL, PASS, 128, 128, 2, 2>(p, grid_y, stream);
+    if (p.NC >= 64) return launch_rect<DIL, PASS, 128, 64, 2, 2>(p, grid_y, stream);
+    return launch_rect<DIL, PASS, 128, 32, 4, 1>(p, grid_y, stream);
 }
 
 // slices of the filter gradient's pixel reduction: enough workgroups for two per CU, at least 4 chunks each, at most 128
@@ -443,15 +479,15 @@ int wgrad_splits(int N, int C, int K, int R, int S, int OH, int OW) {
     return ceil_div(ksteps, per);
 }
 
-}  // namespace
-
-extern "C" int denet_conv_rect_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
-                                   int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
-                                   int OW, hipStream_t stream) {
-    int rc = check_rect("conv_rect_fwd", N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+// The host side of the three passes, one text for both kernels: `who` names the entry point in the messages
+template <bool DIL>
+int rect_fwd(const char* who, const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N, int H,
+             int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
+             hipStream_t stream) {
+    int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     if (rc) return rc;
-    DENET_CHECK_ARG(x && w && y, "conv_rect_fwd: null tensor");
-    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    DENET_CHECK_ARG(x && w && y, "%s: null tensor", who);
+    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     p.a = x; p.b = w; p.out = y; p.bias = bias; p.add = add; p.relu = relu;
     p.M = p.npix; p.NC = K;
     p.ksteps = R * S * C / BK;
@@ -459,17 +495,17 @@ extern "C" int denet_conv_rect_fwd(const float* x, const float* w, const float* 
     p.div_row.init((uint32_t)OW);
     p.a_bytes = (unsigned)((long)N * H * W * C * 4);
     p.b_bytes = (unsigned)((long)K * R * S * C * 4);
-    return launch_by_cols<PASS_FWD>(p, 1, stream);
+    return launch_by_cols<DIL, PASS_FWD>(p, 1, stream);
 }
 
-extern "C" int denet_conv_rect_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
-                                     int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
-                                     hipStream_t stream) {
-    int rc = check_rect("conv_rect_dgrad", N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+template <bool DIL>
+int rect_dgrad(const char* who, const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K, int R,
+               int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW, hipStream_t stream) {
+    int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     if (rc) return rc;
-    DENET_CHECK_ARG(dy && w && dx, "conv_rect_dgrad: null tensor");
-    DENET_CHECK_ARG(C % 32 == 0, "conv_rect_dgrad: physical C (%d) must be a multiple of 32 (the network input has no gradient)", C);
-    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
+    DENET_CHECK_ARG(dy && w && dx, "%s: null tensor", who);
+    DENET_CHECK_ARG(C % 32 == 0, "%s: physical C (%d) must be a multiple of 32 (the network input has no gradient)", who, C);
+    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     p.a = dy; p.b = w; p.out = dx; p.add = add;
     p.Hc = ceil_div(H, sh); p.Wc = ceil_div(W, sw);
     p.M = N * p.Hc * p.Wc; p.NC = C;
@@ -477,7 +513,60 @@ extern "C" int denet_conv_rect_dgrad(const float* dy, const float* w, const floa
     p.div_row.init((uint32_t)p.Wc);
     p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
     p.b_bytes = (unsigned)((long)K * R * S * C * 4);
-    return launch_by_cols<PASS_DGRAD>(p, (unsigned)(sh * sw), stream);
+    return launch_by_cols<DIL, PASS_DGRAD>(p, (unsigned)(sh * sw), stream);
+}
+
+template <bool DIL>
+int rect_wgrad(const char* who, const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N, int H,
+               int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
+               hipStream_t stream) {
+    int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
+    if (rc) return rc;
+    DENET_CHECK_ARG(x && dy && dw_out, "%s: null tensor", who);
+    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
+    p.a = dy; p.b = x;
+    p.M = K; p.NC = R * S * C;
+    p.ksteps = ceil_div(p.npix, BK);
+    const int splits = wgrad_splits(N, C, K, R, S, OH, OW);
+    p.steps_per_split = ceil_div(p.ksteps, splits);
+    p.split_stride = (long)K * p.NC;
+    if (splits > 1) {
+        DENET_CHECK_ARG(workspace && workspace_bytes >= (size_t)splits * p.split_stride * sizeof(float),
+                        "%s: workspace of %zu bytes, %zu needed (denet_conv_rect_wgrad_workspace_bytes)", who, workspace_bytes,
+                        (size_t)splits * p.split_stride * sizeof(float));
+        p.out = workspace;
+    } else {
+        p.out = dw_out;
+    }
+    p.div_img.init((uint32_t)(OH * OW));
+    p.div_row.init((uint32_t)OW);
+    p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
+    p.b_bytes = (unsigned)((long)N * H * W * C * 4);
+    if (K >= 96) rc = launch_rect<DIL, PASS_WGRAD, 128, 128, 2, 2>(p, (unsigned)splits, stream);
+    else if (K >= 64) rc = launch_rect<DIL, PASS_WGRAD, 64, 128, 2, 2>(p, (unsigned)splits, stream);
+    else rc = launch_rect<DIL, PASS_WGRAD, 32, 128, 1, 4>(p, (unsigned)splits, stream);
+    if (rc) return rc;
+    if (splits > 1) {
+        const long n4 = p.split_stride / 4;
+        hipLaunchKernelGGL(conv_rect_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, workspace, dw_out, n4,
+                           splits);
+        DENET_CHECK_LAUNCH("conv_rect_reduce");
+    }
+    return DENET_OK;
+}
+
+}  // namespace
+
+extern "C" int denet_conv_rect_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
+                                   int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
+                                   int OW, hipStream_t stream) {
+    return rect_fwd<false>("conv_rect_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, stream);
+}
+
+extern "C" int denet_conv_rect_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
+                                     int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
+                                     hipStream_t stream) {
+    return rect_dgrad<false>("conv_rect_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, stream);
 }
 
 extern "C" size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int R, int S, int OH, int OW) {
@@ -489,36 +578,26 @@ extern "C" size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int
 extern "C" int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N,
                                      int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
                                      int OW, hipStream_t stream) {
-    int rc = check_rect("conv_rect_wgrad", N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
-    if (rc) return rc;
-    DENET_CHECK_ARG(x && dy && dw, "conv_rect_wgrad: null tensor");
-    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, OH, OW);
-    p.a = dy; p.b = x;
-    p.M = K; p.NC = R * S * C;
-    p.ksteps = ceil_div(p.npix, BK);
-    const int splits = wgrad_splits(N, C, K, R, S, OH, OW);
-    p.steps_per_split = ceil_div(p.ksteps, splits);
-    p.split_stride = (long)K * p.NC;
-    if (splits > 1) {
-        DENET_CHECK_ARG(workspace && workspace_bytes >= (size_t)splits * p.split_stride * sizeof(float),
-                        "conv_rect_wgrad: workspace of %zu bytes, %zu needed (denet_conv_rect_wgrad_workspace_bytes)", workspace_bytes,
-                        (size_t)splits * p.split_stride * sizeof(float));
-        p.out = workspace;
-    } else {
-        p.out = dw;
-    }
-    p.div_img.init((uint32_t)(OH * OW));
-    p.div_row.init((uint32_t)OW);
-    p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
-    p.b_bytes = (unsigned)((long)N * H * W * C * 4);
-    if (K >= 96) rc = launch_rect<PASS_WGRAD, 128, 128, 2, 2>(p, (unsigned)splits, stream);
-    else if (K >= 64) rc = launch_rect<PASS_WGRAD, 64, 128, 2, 2>(p, (unsigned)splits, stream);
-    else rc = launch_rect<PASS_WGRAD, 32, 128, 1, 4>(p, (unsigned)splits, stream);
-    if (rc) return rc;
-    if (splits > 1) {
-        const long n4 = p.split_stride / 4;
-        hipLaunchKernelGGL(conv_rect_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, workspace, dw, n4, splits);
-        DENET_CHECK_LAUNCH("conv_rect_reduce");
-    }
-    return DENET_OK;
+    return rect_wgrad<false>("conv_rect_wgrad", x, dy, dw, workspace, workspace_bytes, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1,
+                             OH, OW, stream);
 }
+
+extern "C" int denet_conv_dil_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
+                                  int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw,
+                                  int OH, int OW, hipStream_t stream) {
+    return rect_fwd<true>("conv_dil_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW, stream);
+}
+
+extern "C" int denet_conv_dil_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
+                                    int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
+                                    hipStream_t stream) {
+    return rect_dgrad<true>("conv_dil_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW, stream);
+}
+
+extern "C" int denet_conv_dil_wgrad(const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N,
+                                    int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh,
+                                    int dw, int OH, int OW, hipStream_t stream) {
+    return rect_wgrad<true>("conv_dil_wgrad", x, dy, dw_out, workspace, workspace_bytes, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh,
+                            dw, OH, OW, stream);
+}
+

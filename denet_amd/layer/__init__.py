@@ -68,6 +68,13 @@ def focal_log_lines(model):
             (l.type_name, l.layer_index, l.focal_gamma) for l in walk_layers(model.layers) if getattr(l, "focal_gamma", 0.0) > 0.0]
 
 
+def dilation_log_lines(model):
+    """one line per dilated convolution (nested ones included): its geometry and `dilation (dh, dw)`, for the drivers' start-up log"""
+    from ..model.audit import conv_layers, layer_geometry
+    return ["conv layer %s (%s): dilation %s, direct fp32 kernel (no Winograd, tuned entry, bf16 or fused statistics)" %
+            (name, layer_geometry(l)[1], str(l.dilation)) for name, l in conv_layers(model) if getattr(l, "dilated", False)]
+
+
 class Act:
     """Static activation handle: what `layer.output` is in this build.
 

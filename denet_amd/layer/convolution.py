@@ -43,11 +43,28 @@ def same_crop(border_mode, k):
     return border_mode == "same" and k % 2 == 0
 
 
+def conv_dilation2(dilation, r, s):
+    """(rows, columns) of a layer's dilation (DESIGN.md, "Dilated convolutions"): an integer d is (d, d), a pair is taken as given;
+    every entry an integer >= 1 (ValueError otherwise). On an axis whose filter extent is 1 a dilation has no effect and reads 1"""
+    pair = tuple(dilation) if isinstance(dilation, (tuple, list)) else (dilation, dilation)
+    if len(pair) != 2:
+        raise ValueError("dilation %r: an integer or a pair (rows, columns)" % (dilation,))
+    for d in pair:
+        if isinstance(d, bool) or not isinstance(d, (int, numpy.integer)) or d < 1:
+            raise ValueError("dilation %r: every entry must be an integer >= 1" % (dilation,))
+    return (int(pair[0]) if r > 1 else 1, int(pair[1]) if s > 1 else 1)
+
+
+def effective_extent(k, d):
+    """the span of a k-tap filter axis whose taps lie d apart"""
+    return (k - 1) * d + 1
+
+
 class ConvLayer(AbstractLayer):
     type_name = "conv"
 
     def __init__(self, layers, filter_shape=None, filter_stride=(1, 1), use_bias=False, border_mode="half",
-                 wb="he-backward", json_param={}):
+                 wb="he-backward", json_param={}, dilation=(1, 1)):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -89,14 +106,33 @@ class ConvLayer(AbstractLayer):
         # a layer whose filter, stride or padding differs between rows and columns (`C.X`, an `R` head behind a non-square map)
         # runs the per-axis kernels of csrc/conv_rect.hip (ops.conv_rect_*) and carries its padding as a pair; a square layer keeps
         # the scalar padding and every line of the square path (tuned decisions, Winograd, fused statistics)
-        pad2 = conv_padding2(self.border_mode, fs[2], fs[3])
+        # a dilated layer (`C.D`, `C.DX`, the JSON key "dilation"; DESIGN.md, "Dilated convolutions"): the taps of an axis lie d apart,
+        # the border modes and the output size work on the effective extent ke = (k - 1) * d + 1, the filter and its
+        # initialisation bound stay as they are. It runs the same direct kernels with dilated taps (ops.conv_dil_*)
+        self.dilation = conv_dilation2(json_param.get("dilation", dilation), fs[2], fs[3])
+        self.dilated = self.dilation != (1, 1)
+        ke = (effective_extent(fs[2], self.dilation[0]), effective_extent(fs[3], self.dilation[1]))
+        pad2 = conv_padding2(self.border_mode, ke[0], ke[1])
         self.anisotropic = fs[2] != fs[3] or self.stride[0] != self.stride[1] or pad2[0] != pad2[1]
-        self.pad = pad2 if self.anisotropic else pad2[0]
+        self.pad = pad2 if self.direct else pad2[0]
         if self.border_mode == "same":
             assert self.stride == (1, 1)
 
         # device geometry: physical channels, padded taps for the small-C first layer
         self.cp = self.input.cp
+        if self.dilated:
+            for axis, name in ((0, "row"), (1, "column")):
+                if self.dilation[axis] > 1 and self.stride[axis] != 1:
+                    raise ValueError("conv layer %i: %s dilation %i with %s stride %i - a dilated axis takes stride 1 only"
+                                     % (self.layer_index, name, self.dilation[axis], name, self.stride[axis]))
+            if self.cp < 32:
+                raise ValueError("conv layer %i: a dilated layer needs 32 physical input channels or more (this input has %i: the "
+                                 "raw image)" % (self.layer_index, self.cp))
+            for axis, name in ((0, "rows"), (1, "columns")):
+                padded = self.input_shape[2 + axis] + 2 * pad2[axis]
+                if ke[axis] > padded:
+                    raise ValueError("conv layer %i: effective filter extent %i (%i taps, dilation %i) is larger than the padded "
+                                     "map's %i %s" % (self.layer_index, ke[axis], fs[2 + axis], self.dilation[axis], padded, name))
         self.kp = round_up(fs[0], 32)
         self.s_pad = fs[3] if self.cp >= 32 else round_up(fs[3], 32 // self.cp)
         self.omega = Param(w, "conv omega", "conv", (self.kp, fs[2], self.s_pad, self.cp), s_real=fs[3])
@@ -104,28 +140,41 @@ class ConvLayer(AbstractLayer):
             self.beta = Param(numpy.zeros((fs[0],)), "conv beta", "vector", (self.kp,))
 
         # output shape (convolution.py:55-74)
-        oh = int(math.ceil((self.input_shape[-2] + 2 * pad2[0] - fs[2] + 1) / self.stride[0]))
-        ow = int(math.ceil((self.input_shape[-1] + 2 * pad2[1] - fs[3] + 1) / self.stride[1]))
+        oh = int(math.ceil((self.input_shape[-2] + 2 * pad2[0] - ke[0] + 1) / self.stride[0]))
+        ow = int(math.ceil((self.input_shape[-1] + 2 * pad2[1] - ke[1] + 1) / self.stride[1]))
         # `same` with an even filter: the passes get the output size explicitly (ops.conv_geom's ohw), None = the derived one
         self.ohw = None
-        if same_crop(self.border_mode, fs[2]) or same_crop(self.border_mode, fs[3]):
+        if same_crop(self.border_mode, ke[0]) or same_crop(self.border_mode, ke[1]):
             oh, ow = self.input_shape[-2], self.input_shape[-1]
             self.ohw = (oh, ow)
         self.output_shape = (self.input_shape[0], fs[0], oh, ow)
         self.output = Act(self.output_shape, self.kp, "conv%i" % self.layer_index)
 
+    @property
+    def direct(self):
+        """the layer runs the direct per-axis kernels of csrc/conv_rect.hip - ops.conv_rect_*, dilated ops.conv_dil_* - and none of
+        the square path: no tuned decision, no Winograd, no bf16 kernel, no fused statistics or skip add"""
+        return self.anisotropic or self.dilated
+
     @staticmethod
     def parse_desc(layers, name, tags, params):
+        """C[k, size, stride], C.X[k, kh, kw, sh, sw]; the D tag appends the dilation: C.D[k, size, stride, d],
+        C.DX[k, kh, kw, sh, sw, dh, dw]; B: with bias"""
         if name != "C":
             return False
         use_bias = bool("B" in tags)
+        extra = {}                                 # (a token without the D tag makes the constructor call it always made)
         if bool("X" in tags):
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1), params.get(2))
             filter_stride = (params.get(3, 1), params.get(4, 1))
+            if "D" in tags:
+                extra["dilation"] = (params.get(5, 1), params.get(6, 1))
         else:
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1, 1), params.get(1, 1))
             filter_stride = (params.get(2, 1), params.get(2, 1))
-        layers.append(ConvLayer(layers, filter_shape, filter_stride, use_bias, params["borderMode"], params["wb"]))
+            if "D" in tags:
+                extra["dilation"] = (params.get(3, 1), params.get(3, 1))
+        layers.append(ConvLayer(layers, filter_shape, filter_stride, use_bias, params["borderMode"], params["wb"], **extra))
         return True
 
     def weights(self):
@@ -153,6 +202,8 @@ class ConvLayer(AbstractLayer):
                      "useBias": self.use_bias,
                      "bias": self.beta.get_value() if self.use_bias else None,
                      "weight": self.omega.get_value()})
+        if tuple(self.dilation) != (1, 1):
+            json["dilation"] = self.dilation       # (written by dilated layers only: every other model saves what it saved before)
         return json
 
     # ---- execution ----
@@ -171,12 +222,12 @@ class ConvLayer(AbstractLayer):
 
     def forward(self, ctx, add=None):
         from . import get_train
-        if self.anisotropic:
+        if self.direct:
             # the direct per-axis kernel on the plain tensor: a pending input is written first (Act.data), no skip add or
             # statistics in the epilogue - the layers behind run their own passes
-            self.output.data = ops.conv_rect_fwd(self.input.data, self._w(), bias=self.beta.dev if self.use_bias else None, add=add,
-                                                 stride=self.stride, pad=self.pad, s_real=self.filter_shape[3],
-                                                 logical=self._logical(), cache=self._cache(), ohw=self.ohw)
+            fwd, _, _, kw = self._direct_calls()
+            self.output.data = fwd(self.input.data, self._w(), bias=self.beta.dev if self.use_bias else None, add=add,
+                                   logical=self._logical(), cache=self._cache(), **kw)
             self.output.stats = None
             return
         # the input may be the output of a batch norm whose pointwise pass is still pending (ops.BnLink): a Winograd pass runs it
@@ -235,6 +286,14 @@ class ConvLayer(AbstractLayer):
         self._settle_up(up)
         self.output.stats = cache.pop("bn_stats", None) if want_stats else None
 
+    def _direct_calls(self):
+        """(fwd, dgrad, wgrad, their geometry arguments) of a direct layer: a dilated one takes the conv_dil_* calls, an undilated
+        anisotropic one keeps conv_rect_*"""
+        kw = dict(stride=self.stride, pad=self.pad, s_real=self.filter_shape[3], ohw=self.ohw)
+        if self.dilated:
+            return ops.conv_dil_fwd, ops.conv_dil_dgrad, ops.conv_dil_wgrad, dict(kw, dilation=self.dilation)
+        return ops.conv_rect_fwd, ops.conv_rect_dgrad, ops.conv_rect_wgrad, kw
+
     def _record_mode(self, cache, training):
         """what ops.conv_fwd / conv_dgrad / conv_wgrad read about this pass in the layer's cache -> cache["bf16_train"]"""
         cache["train"] = training and self.enabled and self.omega.grad is not None
@@ -249,12 +308,12 @@ class ConvLayer(AbstractLayer):
         return cache["bf16_train"]
 
     def _bf16_train_eligible(self):
-        """the layers ops.TRAIN_PRECISION = "bf16" moves ("bf16 training"): square, not anisotropic, 32 physical input
+        """the layers ops.TRAIN_PRECISION = "bf16" moves ("bf16 training"): square, not anisotropic or dilated, 32 physical input
         channels or more (never the stem), every tap real, a stride that is a power of two (the bf16 kernels take no other), no cut
         output, not kept in fp32 (a softmax reads the output)"""
         fs = self.filter_shape
         st = self.stride[0]
-        return (type(self) is ConvLayer and not self.anisotropic and fs[2] == fs[3] and self.cp % 32 == 0 and self.s_pad == fs[3]
+        return (type(self) is ConvLayer and not self.direct and fs[2] == fs[3] and self.cp % 32 == 0 and self.s_pad == fs[3]
                 and st > 0 and st & (st - 1) == 0 and self.ohw is None and not getattr(self, "fp32_only", False))
 
     def _settle_up(self, up):
@@ -277,9 +336,9 @@ class ConvLayer(AbstractLayer):
             w_f, b_f = ops.bn_fold(self._w(), self.beta.dev if self.use_bias else None, bn.omega.dev, bn.beta.dev,
                                    bn.mean.dev, bn.stdinv.dev, bn.eps)
             ent = cache["fold"] = (ops.WEIGHTS_VERSION, bn, w_f, b_f)
-        if self.anisotropic:
-            y = ops.conv_rect_fwd(self.input.data, ent[2], bias=ent[3], add=add, stride=self.stride, pad=self.pad,
-                                  s_real=self.filter_shape[3], logical=self._logical(), cache=cache, relu=relu, ohw=self.ohw)
+        if self.direct:
+            fwd, _, _, kw = self._direct_calls()
+            y = fwd(self.input.data, ent[2], bias=ent[3], add=add, logical=self._logical(), cache=cache, relu=relu, **kw)
             self.output.data = y
             (out_act if out_act is not None else bn.output).data = y
             return y
@@ -301,21 +360,21 @@ class ConvLayer(AbstractLayer):
         return y
 
     def _backward_rect(self, ctx):
-        """backward of an anisotropic layer: filter gradient on the second stream, bias gradient by column sums, data gradient"""
+        """backward of a direct layer (anisotropic or dilated): filter gradient on the second stream, bias gradient by column
+        sums, data gradient"""
         dy = self.output.grad
         x = self.input.data
+        _, dgrad, wgrad, kw = self._direct_calls()
         if self.enabled and self.omega.grad is not None:
             with ops.wgrad_stream():
-                ops.conv_rect_wgrad(x, dy, self.omega.dev_shape, stride=self.stride, pad=self.pad, s_real=self.filter_shape[3],
-                                    out=self.omega.grad.view(self.omega.dev_shape), logical=self._logical(), ohw=self.ohw)
+                wgrad(x, dy, self.omega.dev_shape, out=self.omega.grad.view(self.omega.dev_shape), logical=self._logical(), **kw)
                 if self.use_bias:
                     ops.colsum(dy.view(-1, self.kp), out=self.beta.grad)
         if getattr(self.input, "requires_grad", True):
-            self.input.grad = ops.conv_rect_dgrad(dy, self._w(), tuple(x.shape), add=self.input.grad, stride=self.stride,
-                                                  pad=self.pad, s_real=self.filter_shape[3], logical=self._logical(), ohw=self.ohw)
+            self.input.grad = dgrad(dy, self._w(), tuple(x.shape), add=self.input.grad, logical=self._logical(), **kw)
 
     def backward(self, ctx):
-        if self.anisotropic:
+        if self.direct:
             return self._backward_rect(ctx)
         # (the first layer on the planar network input has no data gradient and reads the image as it is)
         planar = getattr(self, "_planar_x", None) if not getattr(self.input, "requires_grad", True) else None

@@ -45,6 +45,9 @@ class DeconvLayer(AbstractLayer):
         self.stride = tuple(json_param.get("stride", filter_stride))
         self.use_bias = json_param.get("useBias", use_bias)
         self.size = (self.filter_shape[2], self.filter_shape[3])
+        if "dilation" in json_param:
+            raise ValueError("deconv layer %i: a transposed convolution takes no dilation (the key \"dilation\" belongs to conv and "
+                             "resnet layers)" % self.layer_index)
 
         fs = self.filter_shape
         # deconvolution.py:27-37
@@ -92,6 +95,8 @@ class DeconvLayer(AbstractLayer):
     def parse_desc(layers, name, tags, params):
         if name != "DC":
             return False
+        if "D" in tags:
+            raise ValueError("DC.%s: a transposed convolution takes no dilation (the D tag belongs to `C` layers)" % tags)
         use_bias = bool("B" not in tags)
         if bool("X" in tags):
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1), params.get(2))

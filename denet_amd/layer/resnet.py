@@ -15,7 +15,7 @@ class ResnetLayer(AbstractLayer):
     type_name = "resnet"
 
     def __init__(self, layers, filter_shape=None, stride=(1, 1), bottleneck=0, activation="relu", version="original",
-                 json_param={}):
+                 json_param={}, dilation=1):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -25,6 +25,15 @@ class ResnetLayer(AbstractLayer):
         self.version = json_param.get("version", version)
         self.activation = check_activation(json_param.get("activation", activation))
         self.bn_json_param = json_param.get("bnParam", {"enabled": json_param.get("enableBatchNorm", True)})
+        # a dilated block (`RSN[k, size, stride, bottleneck, d]`, the JSON key "dilation"; DESIGN.md, "Dilated convolutions"): every
+        # convolution of the main path whose extent is above 1 - both of a basic block, the middle one of a bottleneck - has its
+        # taps d apart; the 1x1 convolutions and the projection shortcut stay as they are. A dilated axis takes stride 1 only
+        self.dilation = json_param.get("dilation", dilation)
+        if isinstance(self.dilation, bool) or not isinstance(self.dilation, int) or self.dilation < 1:
+            raise ValueError("resnet layer %i: dilation %r must be an integer >= 1" % (self.layer_index, self.dilation))
+        if self.dilation > 1 and self.stride != (1, 1):
+            raise ValueError("resnet layer %i: dilation %i with stride %s - a dilated block takes stride 1 only"
+                             % (self.layer_index, self.dilation, self.stride))
 
         fs = self.filter_shape
         if self.bottleneck > 0:
@@ -51,9 +60,9 @@ class ResnetLayer(AbstractLayer):
         if "pre-activation" in self.version:
             add_bn_act(self.layers)
         self.layers.append(ConvLayer(self.layers, filter_shape=shape0, filter_stride=self.stride, border_mode="half",
-                                     use_bias=False))
+                                     use_bias=False, dilation=self.dilation))
         add_bn_act(self.layers)
-        self.layers.append(ConvLayer(self.layers, filter_shape=shape1, border_mode="half", use_bias=False))
+        self.layers.append(ConvLayer(self.layers, filter_shape=shape1, border_mode="half", use_bias=False, dilation=self.dilation))
         if self.bottleneck > 0:
             add_bn_act(self.layers)
             self.layers.append(ConvLayer(self.layers, filter_shape=shape2, border_mode="half", use_bias=False))
@@ -80,15 +89,17 @@ class ResnetLayer(AbstractLayer):
             version = "original" if "O" in tags else "pre-activation"
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1), params.get(1))
             filter_stride = (params.get(2, 1), params.get(2, 1))
-            layers.append(ResnetLayer(layers, filter_shape, filter_stride, params.get(3, 0), params["activation"], version))
+            extra = {"dilation": params[4]} if 4 in params else {}        # (without it: the constructor call it always was)
+            layers.append(ResnetLayer(layers, filter_shape, filter_stride, params.get(3, 0), params["activation"], version, **extra))
             return True
         elif name == "nRSN":
             version = "original" if "O" in tags else "pre-activation"
             bottleneck = params.get(4, 0)
+            extra = {"dilation": params[5]} if 5 in params else {}
             for i in range(params.get(0)):
                 filter_shape = (params.get(1), layers[-1].output_shape[1], params.get(2), params.get(2))
                 filter_stride = (params.get(3, 1), params.get(3, 1)) if i == 0 else (1, 1)
-                layers.append(ResnetLayer(layers, filter_shape, filter_stride, bottleneck, params["activation"], version))
+                layers.append(ResnetLayer(layers, filter_shape, filter_stride, bottleneck, params["activation"], version, **extra))
             return True
         return False
 
@@ -114,6 +125,8 @@ class ResnetLayer(AbstractLayer):
         json = super().export_json()
         json.update({"shape": self.filter_shape, "stride": self.stride, "bottleneck": self.bottleneck,
                      "bnParam": self.bn_json_param, "activation": self.activation, "version": self.version})
+        if self.dilation != 1:
+            json["dilation"] = self.dilation       # (written by dilated blocks only)
         json.update({"layers": [layer.export_json() for layer in self.layers]})
         return json
 

@@ -29,8 +29,15 @@ def conv_layers(model):
 
 def layer_geometry(layer):
     """(fwd geometry tuple of ops.conv_geom, human-readable string) of a ConvLayer on its physical NHWC tensors. An anisotropic
-    layer (filter, stride or padding per axis): the tuple of ops.conv_rect_geom, 14 long; it runs conv_rect_kernel<pass, BM, BN>"""
+    layer (filter, stride or padding per axis): the tuple of ops.conv_rect_geom, 14 long; it runs conv_rect_kernel<pass, BM, BN>.
+    A dilated layer: the tuple of ops.conv_dil_geom, 16 long, the dilation named behind the stride (`3x3/1x1 d2x2`); it runs
+    conv_dil_kernel<pass, BM, BN>"""
     n, _, h, w = layer.input_shape
+    if getattr(layer, "dilated", False):
+        g = ops.conv_dil_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride, layer.pad, layer.dilation,
+                              layer.filter_shape[3], layer.ohw)
+        fs = layer.filter_shape
+        return g, "%dx%d %d->%d %dx%d/%dx%d d%dx%d" % ((h, w, fs[1], fs[0], fs[2], fs[3]) + tuple(layer.stride) + tuple(layer.dilation))
     if getattr(layer, "anisotropic", False):
         g = ops.conv_rect_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride, layer.pad, layer.filter_shape[3], layer.ohw)
         fs = layer.filter_shape
@@ -48,7 +55,7 @@ def decisions_cover(model):
     missing = []
     for name, l in conv_layers(model):
         g, txt = layer_geometry(l)
-        if getattr(l, "anisotropic", False):
+        if getattr(l, "direct", False):
             continue                       # one direct kernel, nothing to decide
         three = g[5] == 3 and g[6] == 3 and g[7] == 3 and g[8] == 1 and g[9] == 1 and g[3] >= 32
         if not three:

@@ -402,7 +402,7 @@ class ModelCNN:
             a.skip_behind = None
             if (os.environ.get("DENET_SKIP_FUSE", "1") != "0" and a.type_name == "conv" and b.type_name == "skip"
                     and getattr(b, "combine_mode", None) == "proj-add" and len(getattr(b, "layers", [])) <= 1 and b.x is a.output
-                    and self._consumers(a.output) == 1 and not a.use_bias and not a.anisotropic):
+                    and self._consumers(a.output) == 1 and not a.use_bias and not a.direct):
                 a.skip_behind = b
         if not skip_build:
             self.pack_device()

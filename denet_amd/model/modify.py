@@ -214,7 +214,15 @@ def modify_layer(model, layer_name, assignments):
         for a in assignments:
             name, text = a.split("=")
             old = getattr(layer, name)
-            value = {"True": True, "False": False, "0": False, "1": True}[text] if type(old) is bool else type(old)(text)
+            if type(old) is bool:
+                value = {"True": True, "False": False, "0": False, "1": True}[text]
+            elif type(old) is tuple:
+                # a pair-typed attribute (stride, dilation): `dilation=2` -> (2, 2), `dilation=2,3` -> (2, 3)
+                from .. import common
+                parts = tuple(common.convert_num(t) for t in text.split(","))
+                value = parts * len(old) if len(parts) == 1 else parts
+            else:
+                value = type(old)(text)
             setattr(layer, name, value)
         after = layer.export_json()
         if after == before:

@@ -53,8 +53,10 @@ def kernel_symbol(kind, a, b, c):
         return "dgrad_s2_kernel<%d>" % a
     if kind == 20:
         return "conv_rect_kernel<%d, %d, %d>" % (a, b, c)      # pass (0 fwd / 1 dgrad / 2 wgrad), tile BM x BN
+    if kind == 25:
+        return "conv_dil_kernel<%d, %d, %d>" % (a, b, c)       # the same passes and tiles with dilated taps (`C.D`, `C.DX`)
     if kind == 21:
-        return "conv_bf16_kernel<%d, %d>" % (a, b)             # tile BM x BN of the opt-in bf16 kernel (forward, data gradient)
+        return "conv_bf16_kernel<%d, %d>" % (a, b)            # tile BM x BN of the opt-in bf16 kernel (forward, data gradient)
     if kind == 22:
         return "conv_bf16_wgrad_kernel<%d, %d>" % (a, b)       # tile BM x BN of the opt-in bf16 filter gradient
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
@@ -1435,6 +1437,72 @@ def conv_rect_wgrad(x, dy, w_shape, stride=(1, 1), pad=(0, 0), s_real=None, out=
           "conv_rect_wgrad")
     if PROFILE is not None:
         PROFILE.add(_conv_rect_flops(g, logical))
+    return dw
+
+
+# ---- dilated convolution (csrc/conv_rect.hip, conv_dil_kernel: the same text with the taps (dh, dw) apart): `C.D` / `C.DX` layers
+# and dilated residual blocks ("Dilated convolutions"). As the rectangular calls: one direct kernel per pass, never in a
+# tuned table, no Winograd, no bf16, no fused statistics.
+def conv_dil_geom(x_shape, w_shape, stride, pad, dilation, s_real=None, ohw=None):
+    """the geometry tuple of the denet_conv_dil_* calls: (N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW); the output
+    size is the one of the effective extent ke = (k - 1) * d + 1 per axis"""
+    N, H, W, C = x_shape
+    K, R, S, Cw = w_shape
+    assert Cw == C, (x_shape, w_shape)
+    (sh, sw), (ph, pw), (dh, dw) = stride, pad, dilation
+    s_real = S if s_real is None else s_real
+    keh, kew = (R - 1) * dh + 1, (s_real - 1) * dw + 1
+    if keh > H + 2 * ph or kew > W + 2 * pw:
+        raise ValueError("dilated filter: effective extent %dx%d (filter %dx%d, dilation %dx%d) is larger than the padded map %dx%d"
+                         % (keh, kew, R, s_real, dh, dw, H + 2 * ph, W + 2 * pw))
+    OH = (H + 2 * ph - keh) // sh + 1 if sh > 0 else 0
+    OW = (W + 2 * pw - kew) // sw + 1 if sw > 0 else 0
+    if ohw is not None:
+        assert 0 < ohw[0] <= OH and 0 < ohw[1] <= OW, (ohw, OH, OW)
+        OH, OW = int(ohw[0]), int(ohw[1])
+    return tuple(int(v) for v in (N, H, W, C, K, R, S, s_real, sh, sw, ph, pw, dh, dw, OH, OW))
+
+
+def _conv_dil_flops(g, logical=None):
+    return _conv_rect_flops(g[:12] + g[14:], logical)
+
+
+def conv_dil_fwd(x, w, bias=None, add=None, stride=(1, 1), pad=(0, 0), dilation=(1, 1), s_real=None, out=None, logical=None,
+                 cache=None, relu=False, ohw=None):
+    x = _settled(x)
+    g = conv_dil_geom(x.shape, w.shape, stride, pad, dilation, s_real, ohw)
+    y = out if out is not None else empty(g[0], g[14], g[15], g[4])
+    if cache is not None:
+        cache["bn_stats"] = None               # the batch norm behind measures its own statistics
+    check(_L().denet_conv_dil_fwd(ptr(x), ptr(w), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_dil_fwd")
+    if PROFILE is not None:
+        PROFILE.add(_conv_dil_flops(g, logical))
+    return y
+
+
+def conv_dil_dgrad(dy, w, x_shape, add=None, stride=(1, 1), pad=(0, 0), dilation=(1, 1), s_real=None, out=None, logical=None,
+                   ohw=None):
+    g = conv_dil_geom(x_shape, w.shape, stride, pad, dilation, s_real, ohw)
+    assert tuple(dy.shape) == (g[0], g[14], g[15], g[4]), (dy.shape, g)
+    dx = out if out is not None else empty(*x_shape)
+    check(_L().denet_conv_dil_dgrad(ptr(dy), ptr(w), ptr(add), ptr(dx), *g, stream_ptr()), "conv_dil_dgrad")
+    if PROFILE is not None:
+        PROFILE.add(_conv_dil_flops(g, logical))
+    return dx
+
+
+def conv_dil_wgrad(x, dy, w_shape, stride=(1, 1), pad=(0, 0), dilation=(1, 1), s_real=None, out=None, logical=None, ohw=None):
+    x = _settled(x)
+    g = conv_dil_geom(x.shape, w_shape, stride, pad, dilation, s_real, ohw)
+    assert tuple(dy.shape) == (g[0], g[14], g[15], g[4]), (dy.shape, g)
+    dw = out if out is not None else empty(*w_shape)
+    N, H, W, C, K, R, S = g[:7]
+    nbytes = int(_L().denet_conv_rect_wgrad_workspace_bytes(N, C, K, R, S, g[14], g[15]))
+    ws = WS.get("wgrad_rect", nbytes) if nbytes else None
+    check(_L().denet_conv_dil_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(ws), ws.numel() if ws is not None else 0, *g, stream_ptr()),
+          "conv_dil_wgrad")
+    if PROFILE is not None:
+        PROFILE.add(_conv_dil_flops(g, logical))
     return dw
 
 

@@ -218,6 +218,22 @@ size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int R, int S, 
 int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H,
                           int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
                           hipStream_t stream);
+/* ---- Dilated convolution (csrc/conv_rect.hip, the same kernel text with the taps apart): the `C.D[k, size, stride, d]` and
+ *      `C.DX[k, kh, kw, sh, sw, dh, dw]` tokens and the dilated residual blocks. The reference has no such parameter; the contract
+ *      is this build's own ("Dilated convolutions"). Arguments as the denet_conv_rect_* twins, with the dilation
+ *      (dh, dw) >= 1 behind pw: tap (r, s) reads input row oy*sh - ph + r*dh, column ox*sw - pw + s*dw, zero outside the map.
+ *      The effective extent per axis is ke = (k - 1) * d + 1: OH <= (H + 2*ph - ke_h) / sh + 1, OW likewise. Refused: a stride
+ *      other than 1 on an axis with d > 1, and a dilated filter on fewer than 32 physical channels. Dilation (1, 1) computes what
+ *      the denet_conv_rect_* twin computes, bit for bit. The filter gradient takes the workspace of
+ *      denet_conv_rect_wgrad_workspace_bytes and is bit-identical from run to run.                                            */
+int denet_conv_dil_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N, int H,
+                       int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
+                       hipStream_t stream);
+int denet_conv_dil_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K, int R,
+                         int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW, hipStream_t stream);
+int denet_conv_dil_wgrad(const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N, int H,
+                         int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH,
+                         int OW, hipStream_t stream);
 /* ---- OPT-IN bf16 inference (csrc/conv_bf16.hip), never the fp32 path and never taken by training: the forward pass of a square
  *      convolution (geometry and tensors as denet_conv_fwd_act; C % 32 = 0, every tap real) with both operands rounded to bf16,
  *          y = epilogue( sum over taps and channels of bf16(x) * bf16(w) ),  accumulated in fp32 (v_mfma_f32_32x32x16_bf16).

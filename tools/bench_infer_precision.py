@@ -85,7 +85,7 @@ def kernel_times(model, reps, warmup):
     """alone-times per geometry of the layers bf16 mode moves: [{geometry, layers, fp32 kernels + ms, bf16 kernel + ms}]"""
     geoms = collections.OrderedDict()
     for name, l in audit.conv_layers(model):
-        if getattr(l, "anisotropic", False) or getattr(l, "fp32_only", False) or l.cp % 32:
+        if getattr(l, "direct", False) or getattr(l, "fp32_only", False) or l.cp % 32:
             continue
         g, txt = audit.layer_geometry(l)
         geoms.setdefault(g, [txt, 0])[1] += 1
