@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
+from igemm_matrix import _TunedTable, _igemm_pass, _igemm_tensors
+
 pytestmark = pytest.mark.gpu
 
 
@@ -889,55 +891,6 @@ def test_data_gradient_of_a_1x1_layer_over_the_transposed_filter(hip, case):
     for mode in ("transposed", "prepared"):
         for a, b in zip(out[mode], out["plain"]):
             assert torch.equal(a, b), mode
-
-
-class _TunedTable:
-    """the process's table of measured launch configurations, emptied for the test and put back afterwards"""
-
-    def __enter__(self):
-        import ctypes
-        from denet_amd import ops
-        self.L = ops._L()
-        self.n = self.L.denet_tune_export(None, 0)
-        self.saved = (ctypes.c_int * (14 * max(self.n, 1)))()
-        assert self.L.denet_tune_export(self.saved, self.n) == self.n
-        assert self.L.denet_tune_clear() == 0
-        return self.L
-
-    def __exit__(self, *exc):
-        assert self.L.denet_tune_clear() == 0
-        assert self.L.denet_tune_import(self.saved, self.n) == 0
-        assert self.L.denet_tune_export(None, 0) == self.n
-
-
-def _igemm_pass(L, code, g, t, ws_bytes):
-    """runs pass `code` (denet_conv_plan's codes) of geometry g on the tensors t through the C ABI; returns the output tensor"""
-    from denet_amd.ops import ptr, stream_ptr
-    N, H, W, C, K = g[:5]
-    if code == 0:
-        rc, out = L.denet_conv_fwd(ptr(t["x"]), ptr(t["w"]), None, None, ptr(t["y"]), *g, stream_ptr()), t["y"]
-    elif code == 1:
-        rc, out = L.denet_conv_dgrad(ptr(t["dy"]), ptr(t["w"]), None, ptr(t["dx"]), *g, stream_ptr()), t["dx"]
-    elif code == 5:
-        rc, out = L.denet_conv_dgrad_t(ptr(t["dy"]), ptr(t["wt"]), None, ptr(t["dx"]), None, None, 0, None, *g, stream_ptr()), t["dx"]
-    elif code == 6:
-        rc, out = L.denet_conv_dgrad_1x1t(ptr(t["dy"]), ptr(t["wt"]), None, ptr(t["dx"]), None, None, 0, None, N, H, W, C, K,
-                                          stream_ptr()), t["dx"]
-    else:
-        rc, out = L.denet_conv_wgrad(ptr(t["x"]), ptr(t["dy"]), ptr(t["dw"]), ptr(t["ws"]), ws_bytes, *g, stream_ptr()), t["dw"]
-    assert rc == 0, (code, g, rc, L.denet_last_error())
-    return out
-
-
-def _igemm_tensors(g, seed):
-    N, H, W, C, K, R, S, _, stride, pad, OH, OW = g
-    gen = torch.Generator().manual_seed(seed)
-    t = {"x": torch.randn(N, H, W, C, generator=gen).cuda(), "w": (torch.randn(K, R, S, C, generator=gen) * 0.1).cuda(),
-         "dy": torch.randn(N, OH, OW, K, generator=gen).cuda()}
-    t["wt"] = t["w"].reshape(K, R * S * C).t().contiguous()            # [R][S][C][K]
-    t["y"], t["dx"], t["dw"] = torch.empty_like(t["dy"]), torch.empty_like(t["x"]), torch.empty_like(t["w"])
-    t["ws"] = torch.empty(64 * t["w"].numel(), device="cuda")            # room for 64 split slices
-    return t
 
 
 @pytest.mark.parametrize("code,C,K,R,stride,pad", [
