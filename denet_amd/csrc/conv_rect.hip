@@ -4,7 +4,9 @@
 // of igemm.hip / winograd.hip take ONE stride and ONE pad; this file is the direct kernel of everything else and shares no
 // code path with them. The same text with the taps of a filter (dh, dw) apart is the dilated convolution of the `C.D[k, size,
 // stride, d]` / `C.DX[k, kh, kw, sh, sw, dh, dw]` tokens and the dilated residual blocks (conv_dil_kernel; this build's own
-// contract, DESIGN.md section 19: the reference has no dilation).
+// contract, DESIGN.md section 19: the reference has no dilation). The same text on a channel window of x, w and y is the grouped
+// convolution of the `C.G[k, size, stride, g]` / `C.GX[k, kh, kw, sh, sw, g]` tokens and the grouped residual blocks
+// (conv_grp_kernel, grid.z = the window; this build's own contract, DESIGN.md section 20: the reference has no groups).
 //
 // Layout (HBM):   activations NHWC fp32, filters KRSC fp32 correlation taps (as igemm.hip).
 // Arithmetic:     v_mfma_f32_32x32x2_f32, exact fp32 FMA chain, accumulators in registers.
@@ -54,6 +56,27 @@ struct RectParams {
 };
 static_assert(sizeof(RectParams) == 192, "RectParams: the kernel-argument layout of conv_rect_kernel is part of its device code");
 
+// A grouped pass: the dense problem `r` of ONE channel window (r.C = Cw input and r.K = Kw output channels: the reduction extents
+// and the filter's inner dimension) inside tensors whose pixels hold ldc / ldk channels. Window i = blockIdx.z starts i * Cw
+// channels into x / dx, i * Kw into y / dy / bias / add and i * Kw * R * S * Cw elements into w / dw and each of its slices. A struct
+// of its own: RectParams is the kernel-argument layout of the kernels that came before
+struct GrpParams {
+    RectParams r;
+    int ldc, ldk;        // channels of a whole pixel of x / dx, of y / dy
+    int w_win;           // Kw * R * S * Cw: the filter rows of one window
+};
+
+// what the one text reads of either struct (the plain passes: the pixel strides are the extents, no window). The body calls these
+// at every use: read once into locals, the plain kernels came out with other scalar registers than they had (EXPERIMENTS.md)
+__device__ __forceinline__ const RectParams& rect_of(const RectParams& p) { return p; }
+__device__ __forceinline__ const RectParams& rect_of(const GrpParams& q) { return q.r; }
+__device__ __forceinline__ int ldc_of(const RectParams& p) { return p.C; }
+__device__ __forceinline__ int ldc_of(const GrpParams& q) { return q.ldc; }
+__device__ __forceinline__ int ldk_of(const RectParams& p) { return p.K; }
+__device__ __forceinline__ int ldk_of(const GrpParams& q) { return q.ldk; }
+__device__ __forceinline__ int w_win_of(const RectParams&) { return 0; }
+__device__ __forceinline__ int w_win_of(const GrpParams& q) { return q.w_win; }
+
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 constexpr int OOB_OFFSET = (int)0xF0000000u;   // beyond every extent check_rect admits
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, int elem_off, bool ok) {
@@ -63,9 +86,18 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, int elem_of
 
 // The one text of all three passes. DIL = false: the taps of a filter are neighbours (conv_rect_kernel); DIL = true: they lie
 // (dh, dw) apart (conv_dil_kernel). A dilated axis has stride 1 (check_rect), so the data gradient's classes are those of the
-// strides alone and its tap walk steps by the dilation. Every dilated term sits behind DIL.
-template <bool DIL, int PASS, int BM, int BN, int WM, int WN>
-__device__ __forceinline__ void conv_rect_body(const RectParams p) {
+// strides alone and its tap walk steps by the dilation. Every dilated term sits behind DIL. GRP = true (P = GrpParams): the passes
+// of channel window blockIdx.z (conv_grp_kernel): p.C / p.K stay the extents of the reductions, the pixel strides become the whole
+// tensors' ldc / ldk and every tensor starts at its window. Every grouped term sits behind GRP.
+template <bool DIL, bool GRP, int PASS, int BM, int BN, int WM, int WN, class P>
+__device__ __forceinline__ void conv_rect_body(const P q) {
+    const RectParams& p = rect_of(q);
+    // the window's first element of a, b, the output (and `add`), and its first bias
+    const long win = GRP ? (long)blockIdx.z : 0;
+    const long win_x = win * p.C, win_y = win * p.K, win_w = win * w_win_of(q);
+    const long win_a = PASS == PASS_FWD ? win_x : win_y;
+    const long win_b = PASS == PASS_FWD || PASS == PASS_DGRAD ? win_w : win_x;
+    const long win_o = PASS == PASS_FWD ? win_y : (PASS == PASS_DGRAD ? win_x : win_w);
     const int dh = DIL ? p.dh : 1, dw = DIL ? p.dw : 1;
     constexpr bool A_KIN = (PASS != PASS_WGRAD);
     constexpr bool B_KIN = (PASS == PASS_FWD);
@@ -143,7 +175,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
                 const uint32_t ox = rem - oy * p.OW;
                 a_y[i] = (int)oy * p.sh - p.ph;
                 a_x[i] = (int)ox * p.sw - p.pw + qs;
-                a_off[i] = (((int)n * p.H + a_y[i]) * p.W + a_x[i]) * p.C + qc;
+                a_off[i] = (((int)n * p.H + a_y[i]) * p.W + a_x[i]) * ldc_of(q) + qc;
             }
         }
 #pragma unroll
@@ -165,7 +197,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
                 if ((int)ya * p.sh + dg_py < p.H && (int)xa * p.sw + dg_px < p.W) {
                     a_y[i] = (int)ya + dg_by;
                     a_x[i] = (int)xa + dg_bx;
-                    a_off[i] = (int)n * (p.OH * p.OW * p.K) + 4 * q8;
+                    a_off[i] = (int)n * (p.OH * p.OW * ldk_of(q)) + 4 * q8;
                 }
             }
         }
@@ -178,7 +210,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
     } else {
 #pragma unroll
         for (int i = 0; i < PA; ++i) {
-            a_off[i] = (kra + RPP_A * i) * p.K + m0 + 4 * qa;
+            a_off[i] = (kra + RPP_A * i) * ldk_of(q) + m0 + 4 * qa;
             a_y[i] = 0; a_x[i] = 0;
         }
         const int jg = n0 + 4 * qb;
@@ -192,8 +224,11 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
     }
     const bool wg_rowok = (PASS == PASS_WGRAD) ? (m0 + 4 * qa < p.K) : true;
 
-    const __amdgpu_buffer_rsrc_t r_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.b, 0, p.b_bytes, 0x00020000);
+    // (a window's descriptor starts at the window and ends where the tensor ends)
+    const __amdgpu_buffer_rsrc_t r_a = __builtin_amdgcn_make_buffer_rsrc((void*)(GRP ? p.a + win_a : p.a), 0,
+                                                                         GRP ? p.a_bytes - (unsigned)win_a * 4 : p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc((void*)(GRP ? p.b + win_b : p.b), 0,
+                                                                         GRP ? p.b_bytes - (unsigned)win_b * 4 : p.b_bytes, 0x00020000);
 
     // wave-uniform reduction cursor: fwd (r, s, c0) over the filter, dgrad (r', s', k0) over the taps of the class; wgrad: chunk
     int cur_r = 0, cur_s = 0, cur_c = 0, cur_step = step_begin;
@@ -202,7 +237,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
     auto load_chunk = [&]() {
         if (PASS == PASS_FWD) {
             const int tap_y = DIL ? cur_r * dh : cur_r, tap_x = DIL ? cur_s * dw : cur_s;
-            const int u_off = (tap_y * p.W + tap_x) * p.C + cur_c;
+            const int u_off = (tap_y * p.W + tap_x) * ldc_of(q) + cur_c;
             const bool tap_ok = cur_s + qs < p.S_real;
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
@@ -226,7 +261,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
             for (int i = 0; i < PA; ++i) {
                 const int oy = a_y[i] - (DIL ? cur_r * dh : cur_r), ox = a_x[i] - (DIL ? cur_s * dw : cur_s);
                 const bool ok = ((unsigned)oy < (unsigned)p.OH) && ((unsigned)ox < (unsigned)p.OW);
-                ra[i] = buf_load4(r_a, a_off[i] + (oy * p.OW + ox) * p.K + cur_c, ok);
+                ra[i] = buf_load4(r_a, a_off[i] + (oy * p.OW + ox) * ldk_of(q) + cur_c, ok);
             }
             const int u_offb = cur_c * rsc + ((dg_r0 + (cur_r << p.shs)) * p.S + dg_s0 + (cur_s << p.sws)) * p.C;
 #pragma unroll
@@ -241,7 +276,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
 #pragma unroll
             for (int i = 0; i < PA; ++i) {
                 const bool ok = wg_rowok && (pix0 + kra + RPP_A * i < p.npix);
-                ra[i] = buf_load4(r_a, pix0 * p.K + a_off[i], ok);
+                ra[i] = buf_load4(r_a, pix0 * ldk_of(q) + a_off[i], ok);
             }
 #pragma unroll
             for (int i = 0; i < PB; ++i) {
@@ -253,7 +288,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
                 const int iy = (int)oy * p.sh - p.ph + (DIL ? wg_r * dh : wg_r);
                 const int ix = (int)ox * p.sw - p.pw + (DIL ? wg_s * dw : wg_s);
                 const bool ok = wg_colok && (pix < p.npix) && ((unsigned)iy < (unsigned)p.H) && ((unsigned)ix < (unsigned)p.W);
-                rb[i] = buf_load4(r_b, (((int)n * p.H + iy) * p.W + ix) * p.C + wg_c, ok);
+                rb[i] = buf_load4(r_b, (((int)n * p.H + iy) * p.W + ix) * ldc_of(q) + wg_c, ok);
             }
         }
         ++cur_step;
@@ -329,13 +364,16 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
         __syncthreads();
     }
 
+    float* const out = GRP ? p.out + win_o : p.out;
+    const float* const bias = GRP ? (p.bias ? p.bias + win_y : nullptr) : p.bias;
+    const float* const addp = GRP ? (p.add ? p.add + win_o : nullptr) : p.add;
     // ---------------- epilogue: the lane owns row m = ..+li, columns 8g + 4h .. +3 in registers 4g .. 4g+3 ----------------
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int m = m0 + arow + 32 * i;
         long row = -1;
         if (PASS == PASS_FWD) {
-            if (m < p.M) row = (long)m * p.K;
+            if (m < p.M) row = (long)m * ldk_of(q);
         } else if (PASS == PASS_DGRAD) {
             if (m < p.M) {
                 const uint32_t n = p.div_img.div(m);
@@ -343,7 +381,7 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
                 const uint32_t ya = p.div_row.div(rem);
                 const uint32_t xa = rem - ya * p.Wc;
                 const int iy = (int)ya * p.sh + dg_py, ix = (int)xa * p.sw + dg_px;
-                if (iy < p.H && ix < p.W) row = (((long)n * p.H + iy) * p.W + ix) * p.C;
+                if (iy < p.H && ix < p.W) row = (((long)n * p.H + iy) * p.W + ix) * ldc_of(q);
             }
         } else {
             if (m < p.K) row = (long)blockIdx.y * p.split_stride + (long)m * p.NC;
@@ -356,13 +394,13 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
                 const int n = n0 + wn * (TN * 32) + 32 * j + 8 * g + 4 * lh;
                 if (n >= p.NC) continue;
                 f32x4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                if (PASS == PASS_FWD && p.bias) v += *(const f32x4*)(p.bias + n);
-                if (PASS != PASS_WGRAD && p.add) v += *(const f32x4*)(p.add + row + n);
+                if (PASS == PASS_FWD && bias) v += *(const f32x4*)(bias + n);
+                if (PASS != PASS_WGRAD && addp) v += *(const f32x4*)(addp + row + n);
                 if (PASS == PASS_FWD && p.relu) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) v[t] = fmaxf(v[t], 0.f);
                 }
-                *(f32x4*)(p.out + row + n) = v;
+                *(f32x4*)(out + row + n) = v;
             }
         }
     }
@@ -370,13 +408,52 @@ __device__ __forceinline__ void conv_rect_body(const RectParams p) {
 
 template <int PASS, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void conv_rect_kernel(const RectParams p) {
-    conv_rect_body<false, PASS, BM, BN, WM, WN>(p);
+    conv_rect_body<false, false, PASS, BM, BN, WM, WN>(p);
 }
 
 // the same passes with the taps (dh, dw) apart: the `C.D[...]` / `C.DX[...]` layers and the dilated residual blocks
 template <int PASS, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256) void conv_dil_kernel(const RectParams p) {
-    conv_rect_body<true, PASS, BM, BN, WM, WN>(p);
+    conv_rect_body<true, false, PASS, BM, BN, WM, WN>(p);
+}
+
+// the same passes on channel window blockIdx.z of x, w and y: the `C.G[...]` / `C.GX[...]` layers and the grouped residual blocks
+template <int PASS, int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(256) void conv_grp_kernel(const GrpParams q) {
+    conv_rect_body<false, true, PASS, BM, BN, WM, WN>(q);
+}
+
+// Groups of fewer than 32 channels (Cg = Kg in {1, 2, 4, 8, 16}) run as windows of 32 channels (slabs) on a filter that is dense
+// inside a slab: output channel k of slab k / 32 reads the Cg channels of its own group and zeros for the rest of the slab.
+//   wd[k][r][s][j] = w[k][r][s][j % Cg] if j / Cg == (k % 32) / Cg, else 0            (j < 32; one float4 of wd per thread)
+__global__ __launch_bounds__(256) void grp_expand_kernel(const float* __restrict__ w, float* __restrict__ wd, long n4, int RS,
+                                                         int cgs) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n4) return;
+    const int Cg = 1 << cgs;
+    const long krs = t >> 3;                     // (k, r, s): 8 float4 to its 32 slab channels
+    const int j0 = (int)(t & 7) * 4;
+    const int blk = (int)((krs / RS) & 31) >> cgs;   // the block of the slab this output channel reads
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j = j0 + e;
+        v[e] = (j >> cgs) == blk ? w[krs * Cg + (j & (Cg - 1))] : 0.f;
+    }
+    ((f32x4*)wd)[t] = v;
+}
+
+// ... and the gradient of the compact filter is the diagonal blocks of the slab filter's:
+//   dw[k][r][s][c] = dwd[k][r][s][((k % 32) / Cg) * Cg + c]                             (one element of dw per thread)
+__global__ __launch_bounds__(256) void grp_compact_kernel(const float* __restrict__ dwd, float* __restrict__ dw, long n, int RS,
+                                                          int cgs) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int Cg = 1 << cgs;
+    const long krs = t >> cgs;
+    const int c = (int)(t & (Cg - 1));
+    const int blk = (int)((krs / RS) & 31) >> cgs;
+    dw[t] = dwd[krs * 32 + blk * Cg + c];
 }
 
 // dw = the slices added in slice order (one float4 column per thread)
@@ -434,36 +511,61 @@ RectParams make_params(int N, int H, int W, int C, int K, int R, int S, int S_re
     return p;
 }
 
-template <bool DIL, int PASS, int BM, int BN, int WM, int WN>
-int launch_rect(RectParams& p, unsigned grid_y, hipStream_t stream) {
+// the whole tensors around a window problem: channels of a pixel of x / dx and y / dy, the number of windows (plain passes: 1)
+struct GrpDims {
+    int ldc, ldk, windows;
+};
+
+// what a grouped entry point asks beyond check_rect (which sees the whole tensors): windows of whole 128-byte lines, as many on
+// the input as on the output side
+int check_grp(const char* who, int C, int K, int Cw, int Kw, int S, int S_real) {
+    DENET_CHECK_ARG(Cw > 0 && Cw % 32 == 0, "%s: window Cw (%d) must be a positive multiple of 32", who, Cw);
+    DENET_CHECK_ARG(Kw > 0 && Kw % 32 == 0, "%s: window Kw (%d) must be a positive multiple of 32", who, Kw);
+    DENET_CHECK_ARG(C % Cw == 0, "%s: window Cw (%d) does not divide C (%d)", who, Cw, C);
+    DENET_CHECK_ARG(K % Kw == 0, "%s: window Kw (%d) does not divide K (%d)", who, Kw, K);
+    DENET_CHECK_ARG(C / Cw == K / Kw, "%s: %d input windows (C %d / Cw %d) against %d output windows (K %d / Kw %d)", who, C / Cw, C, Cw,
+                    K / Kw, K, Kw);
+    DENET_CHECK_ARG(S_real == S, "%s: S_real (%d) != S (%d): a grouped filter has no padded taps", who, S_real, S);
+    return DENET_OK;
+}
+
+template <bool DIL, bool GRP, int PASS, int BM, int BN, int WM, int WN>
+int launch_rect(RectParams& p, unsigned grid_y, const GrpDims& gd, hipStream_t stream) {
     constexpr bool A_KIN = (PASS != PASS_WGRAD);
     constexpr bool B_KIN = (PASS == PASS_FWD);
     constexpr int SZA = A_KIN ? BM * LDK : BK * (BM + 4);
     constexpr int SZB = B_KIN ? BN * LDK : BK * (BN + 4);
     constexpr size_t lds = 2 * (size_t)(SZA + SZB) * sizeof(float);
+    static_assert(!(DIL && GRP), "a grouped layer is not dilated");
     void (*const kernel)(const RectParams) = DIL ? conv_dil_kernel<PASS, BM, BN, WM, WN> : conv_rect_kernel<PASS, BM, BN, WM, WN>;
+    void (*const grp_kernel)(const GrpParams) = conv_grp_kernel<PASS, BM, BN, WM, WN>;
     static bool attr_set[DENET_MAX_DEVICES] = {};
-    const hipError_t e = denet_allow_dynamic_lds((const void*)kernel, (int)lds, attr_set);
+    const hipError_t e = denet_allow_dynamic_lds(GRP ? (const void*)grp_kernel : (const void*)kernel, (int)lds, attr_set);
     if (e != hipSuccess) {
         denet_set_error("conv_rect: hipFuncSetAttribute(%zu B LDS): %s", lds, hipGetErrorString(e));
         return -(int)e;
     }
     p.tiles_m = ceil_div(p.M, BM);
     p.tiles_n = ceil_div(p.NC, BN);
-    // ops.kernel_symbol: 20 = conv_rect_kernel<PASS, BM, BN>, 25 = conv_dil_kernel<PASS, BM, BN>
-    const int prof = denet_prof_begin(DIL ? 25 : 20, PASS, BM, BN, stream);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(p.tiles_m * p.tiles_n), grid_y, 1), dim3(256), lds, stream, p);
+    // ops.kernel_symbol: 20 = conv_rect_kernel<PASS, BM, BN>, 25 = conv_dil_kernel<PASS, BM, BN>, 26 = conv_grp_kernel<PASS, BM, BN>
+    const int prof = denet_prof_begin(GRP ? 26 : (DIL ? 25 : 20), PASS, BM, BN, stream);
+    if (GRP) {
+        const GrpParams q = {p, gd.ldc, gd.ldk, p.K * p.R * p.S * p.C};
+        hipLaunchKernelGGL(grp_kernel, dim3((unsigned)(p.tiles_m * p.tiles_n), grid_y, (unsigned)gd.windows), dim3(256), lds, stream, q);
+    } else {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(p.tiles_m * p.tiles_n), grid_y, 1), dim3(256), lds, stream, p);
+    }
     denet_prof_end(prof, stream);
-    DENET_CHECK_LAUNCH(DIL ? "conv_dil" : "conv_rect");
+    DENET_CHECK_LAUNCH(GRP ? "conv_grp" : (DIL ? "conv_dil" : "conv_rect"));
     return DENET_OK;
 }
 
 // rows of 128 pixels against 128 / 64 / 32 output columns (fwd, dgrad)
-template <bool DIL, int PASS>
-int launch_by_cols(RectParams& p, unsigned grid_y, hipStream_t stream) {
-    if (p.NC >= 96) return launch_rect<DIL, PASS, 128, 128, 2, 2>(p, grid_y, stream);
-    if (p.NC >= 64) return launch_rect<DIL, PASS, 128, 64, 2, 2>(p, grid_y, stream);
-    return launch_rect<DIL, PASS, 128, 32, 4, 1>(p, grid_y, stream);
+template <bool DIL, bool GRP, int PASS>
+int launch_by_cols(RectParams& p, unsigned grid_y, const GrpDims& gd, hipStream_t stream) {
+    if (p.NC >= 96) return launch_rect<DIL, GRP, PASS, 128, 128, 2, 2>(p, grid_y, gd, stream);
+    if (p.NC >= 64) return launch_rect<DIL, GRP, PASS, 128, 64, 2, 2>(p, grid_y, gd, stream);
+    return launch_rect<DIL, GRP, PASS, 128, 32, 4, 1>(p, grid_y, gd, stream);
 }
 
 // slices of the filter gradient's pixel reduction: enough workgroups for two per CU, at least 4 chunks each, at most 128
@@ -479,61 +581,68 @@ int wgrad_splits(int N, int C, int K, int R, int S, int OH, int OW) {
     return ceil_div(ksteps, per);
 }
 
-// The host side of the three passes, one text for both kernels: `who` names the entry point in the messages
-template <bool DIL>
+// The host side of the three passes, one text for the three kernels: `who` names the entry point in the messages. C and K are the
+// channels of the whole tensors, Cw and Kw those of one window (the plain passes: Cw = C, Kw = K, one window); the filter is
+// [K][R][S][Cw]
+template <bool DIL, bool GRP = false>
 int rect_fwd(const char* who, const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N, int H,
              int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
-             hipStream_t stream) {
+             int Cw, int Kw, hipStream_t stream) {
     int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     if (rc) return rc;
+    if (GRP && (rc = check_grp(who, C, K, Cw, Kw, S, S_real))) return rc;
     DENET_CHECK_ARG(x && w && y, "%s: null tensor", who);
-    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
+    RectParams p = make_params(N, H, W, Cw, Kw, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     p.a = x; p.b = w; p.out = y; p.bias = bias; p.add = add; p.relu = relu;
-    p.M = p.npix; p.NC = K;
-    p.ksteps = R * S * C / BK;
+    p.M = p.npix; p.NC = Kw;
+    p.ksteps = R * S * Cw / BK;
     p.div_img.init((uint32_t)(OH * OW));
     p.div_row.init((uint32_t)OW);
     p.a_bytes = (unsigned)((long)N * H * W * C * 4);
-    p.b_bytes = (unsigned)((long)K * R * S * C * 4);
-    return launch_by_cols<DIL, PASS_FWD>(p, 1, stream);
+    p.b_bytes = (unsigned)((long)K * R * S * Cw * 4);
+    return launch_by_cols<DIL, GRP, PASS_FWD>(p, 1, GrpDims{C, K, C / Cw}, stream);
 }
 
-template <bool DIL>
+template <bool DIL, bool GRP = false>
 int rect_dgrad(const char* who, const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K, int R,
-               int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW, hipStream_t stream) {
-    int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
-    if (rc) return rc;
-    DENET_CHECK_ARG(dy && w && dx, "%s: null tensor", who);
-    DENET_CHECK_ARG(C % 32 == 0, "%s: physical C (%d) must be a multiple of 32 (the network input has no gradient)", who, C);
-    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
-    p.a = dy; p.b = w; p.out = dx; p.add = add;
-    p.Hc = ceil_div(H, sh); p.Wc = ceil_div(W, sw);
-    p.M = N * p.Hc * p.Wc; p.NC = C;
-    p.div_img.init((uint32_t)(p.Hc * p.Wc));
-    p.div_row.init((uint32_t)p.Wc);
-    p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
-    p.b_bytes = (unsigned)((long)K * R * S * C * 4);
-    return launch_by_cols<DIL, PASS_DGRAD>(p, (unsigned)(sh * sw), stream);
-}
-
-template <bool DIL>
-int rect_wgrad(const char* who, const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N, int H,
-               int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
+               int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW, int Cw, int Kw,
                hipStream_t stream) {
     int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     if (rc) return rc;
+    if (GRP && (rc = check_grp(who, C, K, Cw, Kw, S, S_real))) return rc;
+    DENET_CHECK_ARG(dy && w && dx, "%s: null tensor", who);
+    DENET_CHECK_ARG(C % 32 == 0, "%s: physical C (%d) must be a multiple of 32 (the network input has no gradient)", who, C);
+    RectParams p = make_params(N, H, W, Cw, Kw, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
+    p.a = dy; p.b = w; p.out = dx; p.add = add;
+    p.Hc = ceil_div(H, sh); p.Wc = ceil_div(W, sw);
+    p.M = N * p.Hc * p.Wc; p.NC = Cw;
+    p.div_img.init((uint32_t)(p.Hc * p.Wc));
+    p.div_row.init((uint32_t)p.Wc);
+    p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
+    p.b_bytes = (unsigned)((long)K * R * S * Cw * 4);
+    return launch_by_cols<DIL, GRP, PASS_DGRAD>(p, (unsigned)(sh * sw), GrpDims{C, K, C / Cw}, stream);
+}
+
+template <bool DIL, bool GRP = false>
+int rect_wgrad(const char* who, const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N, int H,
+               int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
+               int Cw, int Kw, hipStream_t stream) {
+    int rc = check_rect(who, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
+    if (rc) return rc;
+    if (GRP && (rc = check_grp(who, C, K, Cw, Kw, S, S_real))) return rc;
     DENET_CHECK_ARG(x && dy && dw_out, "%s: null tensor", who);
-    RectParams p = make_params(N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
+    RectParams p = make_params(N, H, W, Cw, Kw, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW);
     p.a = dy; p.b = x;
-    p.M = K; p.NC = R * S * C;
+    p.M = Kw; p.NC = R * S * Cw;
     p.ksteps = ceil_div(p.npix, BK);
-    const int splits = wgrad_splits(N, C, K, R, S, OH, OW);
+    // (the slices are those of one window's problem: its sums run in the order of the plain pass on that window alone)
+    const int splits = wgrad_splits(N, Cw, Kw, R, S, OH, OW);
     p.steps_per_split = ceil_div(p.ksteps, splits);
     p.split_stride = (long)K * p.NC;
     if (splits > 1) {
         DENET_CHECK_ARG(workspace && workspace_bytes >= (size_t)splits * p.split_stride * sizeof(float),
-                        "%s: workspace of %zu bytes, %zu needed (denet_conv_rect_wgrad_workspace_bytes)", who, workspace_bytes,
-                        (size_t)splits * p.split_stride * sizeof(float));
+                        "%s: workspace of %zu bytes, %zu needed (denet_conv_%s_wgrad_workspace_bytes)", who, workspace_bytes,
+                        (size_t)splits * p.split_stride * sizeof(float), GRP ? "grp" : "rect");
         p.out = workspace;
     } else {
         p.out = dw_out;
@@ -542,9 +651,10 @@ int rect_wgrad(const char* who, const float* x, const float* dy, float* dw_out, 
     p.div_row.init((uint32_t)OW);
     p.a_bytes = (unsigned)((long)N * OH * OW * K * 4);
     p.b_bytes = (unsigned)((long)N * H * W * C * 4);
-    if (K >= 96) rc = launch_rect<DIL, PASS_WGRAD, 128, 128, 2, 2>(p, (unsigned)splits, stream);
-    else if (K >= 64) rc = launch_rect<DIL, PASS_WGRAD, 64, 128, 2, 2>(p, (unsigned)splits, stream);
-    else rc = launch_rect<DIL, PASS_WGRAD, 32, 128, 1, 4>(p, (unsigned)splits, stream);
+    const GrpDims gd = {C, K, C / Cw};
+    if (Kw >= 96) rc = launch_rect<DIL, GRP, PASS_WGRAD, 128, 128, 2, 2>(p, (unsigned)splits, gd, stream);
+    else if (Kw >= 64) rc = launch_rect<DIL, GRP, PASS_WGRAD, 64, 128, 2, 2>(p, (unsigned)splits, gd, stream);
+    else rc = launch_rect<DIL, GRP, PASS_WGRAD, 32, 128, 1, 4>(p, (unsigned)splits, gd, stream);
     if (rc) return rc;
     if (splits > 1) {
         const long n4 = p.split_stride / 4;
@@ -560,13 +670,13 @@ int rect_wgrad(const char* who, const float* x, const float* dy, float* dw_out, 
 extern "C" int denet_conv_rect_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
                                    int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
                                    int OW, hipStream_t stream) {
-    return rect_fwd<false>("conv_rect_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, stream);
+    return rect_fwd<false>("conv_rect_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, C, K, stream);
 }
 
 extern "C" int denet_conv_rect_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
                                      int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
                                      hipStream_t stream) {
-    return rect_dgrad<false>("conv_rect_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, stream);
+    return rect_dgrad<false>("conv_rect_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, C, K, stream);
 }
 
 extern "C" size_t denet_conv_rect_wgrad_workspace_bytes(int N, int C, int K, int R, int S, int OH, int OW) {
@@ -579,25 +689,83 @@ extern "C" int denet_conv_rect_wgrad(const float* x, const float* dy, float* dw,
                                      int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
                                      int OW, hipStream_t stream) {
     return rect_wgrad<false>("conv_rect_wgrad", x, dy, dw, workspace, workspace_bytes, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1,
-                             OH, OW, stream);
+                             OH, OW, C, K, stream);
 }
 
 extern "C" int denet_conv_dil_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
                                   int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw,
                                   int OH, int OW, hipStream_t stream) {
-    return rect_fwd<true>("conv_dil_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW, stream);
+    return rect_fwd<true>("conv_dil_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW, C, K, stream);
 }
 
 extern "C" int denet_conv_dil_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
                                     int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH, int OW,
                                     hipStream_t stream) {
-    return rect_dgrad<true>("conv_dil_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW, stream);
+    return rect_dgrad<true>("conv_dil_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh, dw, OH, OW, C, K, stream);
 }
 
 extern "C" int denet_conv_dil_wgrad(const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N,
                                     int H, int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh,
                                     int dw, int OH, int OW, hipStream_t stream) {
     return rect_wgrad<true>("conv_dil_wgrad", x, dy, dw_out, workspace, workspace_bytes, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, dh,
-                            dw, OH, OW, stream);
+                            dw, OH, OW, C, K, stream);
+}
+
+extern "C" int denet_conv_grp_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N,
+                                  int H, int W, int C, int K, int Cw, int Kw, int R, int S, int S_real, int sh, int sw, int ph, int pw,
+                                  int OH, int OW, hipStream_t stream) {
+    return rect_fwd<false, true>("conv_grp_fwd", x, w, bias, add, y, relu, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, Cw,
+                                 Kw, stream);
+}
+
+extern "C" int denet_conv_grp_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K,
+                                    int Cw, int Kw, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
+                                    hipStream_t stream) {
+    return rect_dgrad<false, true>("conv_grp_dgrad", dy, w, add, dx, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw, 1, 1, OH, OW, Cw, Kw,
+                                   stream);
+}
+
+extern "C" size_t denet_conv_grp_wgrad_workspace_bytes(int N, int C, int K, int Cw, int Kw, int R, int S, int OH, int OW) {
+    if (N <= 0 || C <= 0 || K <= 0 || Cw <= 0 || Kw <= 0 || R <= 0 || S <= 0 || OH <= 0 || OW <= 0) return 0;
+    const int sp = wgrad_splits(N, Cw, Kw, R, S, OH, OW);
+    return sp > 1 ? (size_t)sp * K * R * S * Cw * sizeof(float) : 0;
+}
+
+extern "C" int denet_conv_grp_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N,
+                                    int H, int W, int C, int K, int Cw, int Kw, int R, int S, int S_real, int sh, int sw, int ph,
+                                    int pw, int OH, int OW, hipStream_t stream) {
+    return rect_wgrad<false, true>("conv_grp_wgrad", x, dy, dw, workspace, workspace_bytes, N, H, W, C, K, R, S, S_real, sh, sw, ph, pw,
+                                   1, 1, OH, OW, Cw, Kw, stream);
+}
+
+namespace {
+
+int check_slab(const char* who, const void* a, const void* b, int K, int R, int S, int Cg) {
+    DENET_CHECK_ARG(a && b, "%s: null tensor", who);
+    DENET_CHECK_ARG(K > 0 && K % 32 == 0, "%s: K (%d) must be a positive multiple of 32", who, K);
+    DENET_CHECK_ARG(R > 0 && S > 0, "%s: non-positive filter extent (%d x %d)", who, R, S);
+    DENET_CHECK_ARG(Cg == 1 || Cg == 2 || Cg == 4 || Cg == 8 || Cg == 16, "%s: group size Cg must be 1, 2, 4, 8 or 16 (got %d)", who, Cg);
+    DENET_CHECK_ARG((long)K * R * S * 32 * 4 < 0xF0000000L, "%s: slab filter exceeds the 32-bit buffer extent (3.75 GiB)", who);
+    return DENET_OK;
+}
+
+}  // namespace
+
+extern "C" int denet_conv_grp_expand(const float* w, float* wd, int K, int R, int S, int Cg, hipStream_t stream) {
+    const int rc = check_slab("conv_grp_expand", w, wd, K, R, S, Cg);
+    if (rc) return rc;
+    const long n4 = (long)K * R * S * 8;
+    hipLaunchKernelGGL(grp_expand_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, w, wd, n4, R * S, ilog2_exact(Cg));
+    DENET_CHECK_LAUNCH("conv_grp_expand");
+    return DENET_OK;
+}
+
+extern "C" int denet_conv_grp_compact(const float* dwd, float* dw, int K, int R, int S, int Cg, hipStream_t stream) {
+    const int rc = check_slab("conv_grp_compact", dwd, dw, K, R, S, Cg);
+    if (rc) return rc;
+    const long n = (long)K * R * S * Cg;
+    hipLaunchKernelGGL(grp_compact_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, dwd, dw, n, R * S, ilog2_exact(Cg));
+    DENET_CHECK_LAUNCH("conv_grp_compact");
+    return DENET_OK;
 }
 

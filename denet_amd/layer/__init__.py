@@ -75,6 +75,13 @@ def dilation_log_lines(model):
             (name, layer_geometry(l)[1], str(l.dilation)) for name, l in conv_layers(model) if getattr(l, "dilated", False)]
 
 
+def groups_log_lines(model):
+    """one line per grouped convolution (nested ones included): its geometry and group count, for the drivers' start-up log"""
+    from ..model.audit import conv_layers, layer_geometry
+    return ["conv layer %s (%s): %i groups, direct fp32 kernel (no Winograd, tuned entry, bf16 or fused statistics)" %
+            (name, layer_geometry(l)[1], l.groups) for name, l in conv_layers(model) if getattr(l, "grouped", False)]
+
+
 class Act:
     """Static activation handle: what `layer.output` is in this build.
 

@@ -2,6 +2,7 @@
 export/import_json :114-136). The reference lowers to Theano `conv2d` (a TRUE convolution: flipped filters,
 convolution.py:80-83) and cuDNN; here forward / data-gradient / weight-gradient are the MFMA implicit-GEMM
 kernels of csrc/igemm.hip, the filters being stored flipped in KRSC layout on the device (layer.Param)."""
+import functools
 import math
 
 import numpy
@@ -60,14 +61,25 @@ def effective_extent(k, d):
     return (k - 1) * d + 1
 
 
+def conv_groups(groups, c_in, k_out, who):
+    """the group count of a layer with c_in input and k_out output channels ("Grouped convolutions"): an integer >= 1
+    that divides both (ValueError otherwise, `who` names the layer or token)"""
+    if isinstance(groups, bool) or not isinstance(groups, (int, numpy.integer)) or groups < 1:
+        raise ValueError("%s: groups %r must be an integer >= 1" % (who, groups))
+    if c_in % groups or k_out % groups:
+        raise ValueError("%s: groups %i does not divide both channel counts (%i input, %i output)" % (who, groups, c_in, k_out))
+    return int(groups)
+
+
 class ConvLayer(AbstractLayer):
     type_name = "conv"
 
     def __init__(self, layers, filter_shape=None, filter_stride=(1, 1), use_bias=False, border_mode="half",
-                 wb="he-backward", json_param={}, dilation=(1, 1)):
+                 wb="he-backward", json_param={}, dilation=(1, 1), groups=1):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
+        who = "conv layer %i" % self.layer_index
 
         self.border_mode = json_param.get("border", border_mode)
         if isinstance(self.border_mode, list):
@@ -79,6 +91,17 @@ class ConvLayer(AbstractLayer):
         self.enabled = json_param.get("enabled", True)
 
         fs = self.filter_shape
+        # a grouped layer (`C.G`, `C.GX`, the JSON key "groups"; DESIGN.md, "Grouped convolutions"): g groups, output channel k reads
+        # the fs[1] = C / g input channels of group k // (K / g) only. The filter (K, C / g, R, S), its initialisation bound and the
+        # numpy.random calls below are those of that shape. g == 1 is no grouped layer: everything it was
+        self.groups = json_param.get("groups", groups)
+        if isinstance(self.groups, bool) or not isinstance(self.groups, (int, numpy.integer)) or self.groups < 1:
+            raise ValueError("%s: groups %r must be an integer >= 1" % (who, self.groups))
+        self.groups = int(self.groups)
+        self.grouped = self.groups != 1
+        if self.grouped and (fs[1] * self.groups != self.input_shape[1] or fs[0] % self.groups):
+            raise ValueError("%s: groups %i does not divide both channel counts (%i input channels against %i per group, %i output)"
+                             % (who, self.groups, self.input_shape[1], fs[1], fs[0]))
         # weight initialisation bound (convolution.py:31-40)
         if type(wb) is float or type(wb) is int:
             self.w_bound = float(wb)
@@ -102,7 +125,8 @@ class ConvLayer(AbstractLayer):
         else:
             w = numpy.zeros(shape=fs)
 
-        assert fs[1] == self.input_shape[1], "filter channels %i != input channels %i" % (fs[1], self.input_shape[1])
+        assert fs[1] * self.groups == self.input_shape[1], "filter channels %i x %i groups != input channels %i" % (
+            fs[1], self.groups, self.input_shape[1])
         # a layer whose filter, stride or padding differs between rows and columns (`C.X`, an `R` head behind a non-square map)
         # runs the per-axis kernels of csrc/conv_rect.hip (ops.conv_rect_*) and carries its padding as a pair; a square layer keeps
         # the scalar padding and every line of the square path (tuned decisions, Winograd, fused statistics)
@@ -135,7 +159,25 @@ class ConvLayer(AbstractLayer):
                                      "map's %i %s" % (self.layer_index, ke[axis], fs[2 + axis], self.dilation[axis], padded, name))
         self.kp = round_up(fs[0], 32)
         self.s_pad = fs[3] if self.cp >= 32 else round_up(fs[3], 32 // self.cp)
-        self.omega = Param(w, "conv omega", "conv", (self.kp, fs[2], self.s_pad, self.cp), s_real=fs[3])
+        if self.grouped:
+            if self.dilated:
+                raise ValueError("%s: groups %i with dilation %s - a grouped layer is not dilated" % (who, self.groups, self.dilation))
+            if self.cp < 32:
+                raise ValueError("%s: a grouped layer needs 32 physical input channels or more (this input has %i: the raw image)"
+                                 % (who, self.cp))
+            if self.cp != self.input_shape[1] or self.kp != fs[0]:
+                raise ValueError("%s: a grouped layer takes no padded channels - %i input and %i output channels must be multiples "
+                                 "of 32" % (who, self.input_shape[1], fs[0]))
+            for axis, name in ((0, "row"), (1, "column")):
+                st = self.stride[axis]
+                if st < 1 or st & (st - 1):
+                    raise ValueError("%s: %s stride %i of a grouped layer must be a power of two" % (who, name, st))
+            try:
+                ops.conv_grp_window(self.cp, self.kp, self.groups)       # window path, slab path or refused
+            except ValueError as e:
+                raise ValueError("%s: %s" % (who, e)) from None
+        # the device filter [K][R][S][C] correlation taps; grouped: [K][R][S][C / g] (no padded channel or tap)
+        self.omega = Param(w, "conv omega", "conv", (self.kp, fs[2], self.s_pad, fs[1] if self.grouped else self.cp), s_real=fs[3])
         if self.use_bias:
             self.beta = Param(numpy.zeros((fs[0],)), "conv beta", "vector", (self.kp,))
 
@@ -152,28 +194,39 @@ class ConvLayer(AbstractLayer):
 
     @property
     def direct(self):
-        """the layer runs the direct per-axis kernels of csrc/conv_rect.hip - ops.conv_rect_*, dilated ops.conv_dil_* - and none of
-        the square path: no tuned decision, no Winograd, no bf16 kernel, no fused statistics or skip add"""
-        return self.anisotropic or self.dilated
+        """the layer runs the direct per-axis kernels of csrc/conv_rect.hip - ops.conv_rect_*, dilated ops.conv_dil_*, grouped
+        ops.conv_grp_* - and none of the square path: no tuned decision, no Winograd, no bf16 kernel, no fused statistics or skip add"""
+        return self.anisotropic or self.dilated or self.grouped
 
     @staticmethod
     def parse_desc(layers, name, tags, params):
         """C[k, size, stride], C.X[k, kh, kw, sh, sw]; the D tag appends the dilation: C.D[k, size, stride, d],
-        C.DX[k, kh, kw, sh, sw, dh, dw]; B: with bias"""
+        C.DX[k, kh, kw, sh, sw, dh, dw]; the G tag appends the groups: C.G[k, size, stride, g], C.GX[k, kh, kw, sh, sw, g];
+        B: with bias"""
         if name != "C":
             return False
         use_bias = bool("B" in tags)
-        extra = {}                                 # (a token without the D tag makes the constructor call it always made)
+        extra = {}                                 # (a token without the D or G tag makes the constructor call it always made)
+        if "G" in tags and "D" in tags:
+            raise ValueError("C.%s: the G tag together with the D tag - a grouped layer is not dilated" % tags)
         if bool("X" in tags):
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1), params.get(2))
             filter_stride = (params.get(3, 1), params.get(4, 1))
             if "D" in tags:
                 extra["dilation"] = (params.get(5, 1), params.get(6, 1))
+            if "G" in tags:
+                extra["groups"] = params.get(5, 1)
         else:
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1, 1), params.get(1, 1))
             filter_stride = (params.get(2, 1), params.get(2, 1))
             if "D" in tags:
                 extra["dilation"] = (params.get(3, 1), params.get(3, 1))
+            if "G" in tags:
+                extra["groups"] = params.get(3, 1)
+        if "groups" in extra:
+            # the filter spans the channels of one group: (K, C / g, R, S)
+            g = conv_groups(extra["groups"], filter_shape[1], filter_shape[0], "C.%s" % tags)
+            filter_shape = (filter_shape[0], filter_shape[1] // g) + filter_shape[2:]
         layers.append(ConvLayer(layers, filter_shape, filter_stride, use_bias, params["borderMode"], params["wb"], **extra))
         return True
 
@@ -204,6 +257,8 @@ class ConvLayer(AbstractLayer):
                      "weight": self.omega.get_value()})
         if tuple(self.dilation) != (1, 1):
             json["dilation"] = self.dilation       # (written by dilated layers only: every other model saves what it saved before)
+        if self.groups != 1:
+            json["groups"] = self.groups           # (written by grouped layers only; "shape" is then (K, C / g, R, S))
         return json
 
     # ---- execution ----
@@ -287,9 +342,13 @@ class ConvLayer(AbstractLayer):
         self.output.stats = cache.pop("bn_stats", None) if want_stats else None
 
     def _direct_calls(self):
-        """(fwd, dgrad, wgrad, their geometry arguments) of a direct layer: a dilated one takes the conv_dil_* calls, an undilated
-        anisotropic one keeps conv_rect_*"""
+        """(fwd, dgrad, wgrad, their geometry arguments) of a direct layer: a dilated one takes the conv_dil_* calls, a grouped one
+        conv_grp_* (its data gradient shares the forward pass's slab filter through the layer's cache), an anisotropic one that is
+        neither keeps conv_rect_*"""
         kw = dict(stride=self.stride, pad=self.pad, s_real=self.filter_shape[3], ohw=self.ohw)
+        if self.grouped:
+            return (ops.conv_grp_fwd, functools.partial(ops.conv_grp_dgrad, cache=self._cache()), ops.conv_grp_wgrad,
+                    dict(kw, groups=self.groups))
         if self.dilated:
             return ops.conv_dil_fwd, ops.conv_dil_dgrad, ops.conv_dil_wgrad, dict(kw, dilation=self.dilation)
         return ops.conv_rect_fwd, ops.conv_rect_dgrad, ops.conv_rect_wgrad, kw
@@ -308,7 +367,7 @@ class ConvLayer(AbstractLayer):
         return cache["bf16_train"]
 
     def _bf16_train_eligible(self):
-        """the layers ops.TRAIN_PRECISION = "bf16" moves ("bf16 training"): square, not anisotropic or dilated, 32 physical input
+        """the layers ops.TRAIN_PRECISION = "bf16" moves ("bf16 training"): square, not anisotropic, dilated or grouped, 32 physical input
         channels or more (never the stem), every tap real, a stride that is a power of two (the bf16 kernels take no other), no cut
         output, not kept in fp32 (a softmax reads the output)"""
         fs = self.filter_shape
@@ -360,7 +419,7 @@ class ConvLayer(AbstractLayer):
         return y
 
     def _backward_rect(self, ctx):
-        """backward of a direct layer (anisotropic or dilated): filter gradient on the second stream, bias gradient by column
+        """backward of a direct layer (anisotropic, dilated or grouped): filter gradient on the second stream, bias gradient by column
         sums, data gradient"""
         dy = self.output.grad
         x = self.input.data

@@ -49,6 +49,10 @@ class DeconvLayer(AbstractLayer):
             raise ValueError("deconv layer %i: a transposed convolution takes no dilation (the key \"dilation\" belongs to conv and "
                              "resnet layers)" % self.layer_index)
 
+        if "groups" in json_param:
+            raise ValueError("deconv layer %i: a transposed convolution takes no groups (the key \"groups\" belongs to conv and "
+                             "resnet layers)" % self.layer_index)
+
         fs = self.filter_shape
         # deconvolution.py:27-37
         if type(wb) is float or type(wb) is int:
@@ -97,6 +101,8 @@ class DeconvLayer(AbstractLayer):
             return False
         if "D" in tags:
             raise ValueError("DC.%s: a transposed convolution takes no dilation (the D tag belongs to `C` layers)" % tags)
+        if "G" in tags:
+            raise ValueError("DC.%s: a transposed convolution takes no groups (the G tag belongs to `C` layers)" % tags)
         use_bias = bool("B" not in tags)
         if bool("X" in tags):
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1), params.get(2))

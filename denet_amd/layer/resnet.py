@@ -15,7 +15,7 @@ class ResnetLayer(AbstractLayer):
     type_name = "resnet"
 
     def __init__(self, layers, filter_shape=None, stride=(1, 1), bottleneck=0, activation="relu", version="original",
-                 json_param={}, dilation=1):
+                 json_param={}, dilation=1, groups=1):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -34,18 +34,41 @@ class ResnetLayer(AbstractLayer):
         if self.dilation > 1 and self.stride != (1, 1):
             raise ValueError("resnet layer %i: dilation %i with stride %s - a dilated block takes stride 1 only"
                              % (self.layer_index, self.dilation, self.stride))
+        # a grouped block (`RSN[k, size, stride, bottleneck, d, g]`, the JSON key "groups"; DESIGN.md, "Grouped convolutions"): the
+        # same convolutions - extent above 1: both of a basic block, the middle one of a bottleneck - have g groups; the 1x1
+        # convolutions and the projection shortcut stay dense. A grouped block is not dilated. "shape" stays the block's own
+        self.groups = json_param.get("groups", groups)
+        if isinstance(self.groups, bool) or not isinstance(self.groups, int) or self.groups < 1:
+            raise ValueError("resnet layer %i: groups %r must be an integer >= 1" % (self.layer_index, self.groups))
+        if self.groups > 1 and self.dilation > 1:
+            raise ValueError("resnet layer %i: groups %i with dilation %i - a grouped block is not dilated"
+                             % (self.layer_index, self.groups, self.dilation))
 
         fs = self.filter_shape
+        g = self.groups if fs[2] > 1 or fs[3] > 1 else 1
         if self.bottleneck > 0:
             self.size = (fs[2], fs[3])
             shape0 = (self.bottleneck, fs[1], 1, 1)
             shape1 = (self.bottleneck, self.bottleneck, fs[2], fs[3])
             shape2 = (fs[0], self.bottleneck, 1, 1)
+            grouped = [] if g == 1 else [(1, shape1)]
         else:
             self.size = (fs[2] * 2 - 1, fs[3] * 2 - 1)
             shape0 = fs
             shape1 = (fs[0], fs[0], fs[2], fs[3])
             shape2 = None
+            grouped = [] if g == 1 else [(0, shape0), (1, shape1)]
+        # (an ungrouped block makes the constructor calls it always made)
+        extra = [{}, {}]
+        for i, sh in grouped:
+            if sh[1] % g or sh[0] % g:
+                raise ValueError("resnet layer %i: groups %i does not divide both channel counts (%i input, %i output) of its %ix%i "
+                                 "convolution" % (self.layer_index, g, sh[1], sh[0], sh[2], sh[3]))
+            extra[i] = {"groups": g}
+        if g > 1:
+            shape1 = (shape1[0], shape1[1] // g) + shape1[2:]
+            if self.bottleneck <= 0:
+                shape0 = (shape0[0], shape0[1] // g) + shape0[2:]
 
         fused = ("bnrelu" in self.version) and self.activation == "relu"
 
@@ -60,9 +83,10 @@ class ResnetLayer(AbstractLayer):
         if "pre-activation" in self.version:
             add_bn_act(self.layers)
         self.layers.append(ConvLayer(self.layers, filter_shape=shape0, filter_stride=self.stride, border_mode="half",
-                                     use_bias=False, dilation=self.dilation))
+                                     use_bias=False, dilation=self.dilation, **extra[0]))
         add_bn_act(self.layers)
-        self.layers.append(ConvLayer(self.layers, filter_shape=shape1, border_mode="half", use_bias=False, dilation=self.dilation))
+        self.layers.append(ConvLayer(self.layers, filter_shape=shape1, border_mode="half", use_bias=False, dilation=self.dilation,
+                                     **extra[1]))
         if self.bottleneck > 0:
             add_bn_act(self.layers)
             self.layers.append(ConvLayer(self.layers, filter_shape=shape2, border_mode="half", use_bias=False))
@@ -90,12 +114,16 @@ class ResnetLayer(AbstractLayer):
             filter_shape = (params.get(0), layers[-1].output_shape[1], params.get(1), params.get(1))
             filter_stride = (params.get(2, 1), params.get(2, 1))
             extra = {"dilation": params[4]} if 4 in params else {}        # (without it: the constructor call it always was)
+            if 5 in params:
+                extra["groups"] = params[5]
             layers.append(ResnetLayer(layers, filter_shape, filter_stride, params.get(3, 0), params["activation"], version, **extra))
             return True
         elif name == "nRSN":
             version = "original" if "O" in tags else "pre-activation"
             bottleneck = params.get(4, 0)
             extra = {"dilation": params[5]} if 5 in params else {}
+            if 6 in params:
+                extra["groups"] = params[6]
             for i in range(params.get(0)):
                 filter_shape = (params.get(1), layers[-1].output_shape[1], params.get(2), params.get(2))
                 filter_stride = (params.get(3, 1), params.get(3, 1)) if i == 0 else (1, 1)
@@ -127,6 +155,8 @@ class ResnetLayer(AbstractLayer):
                      "bnParam": self.bn_json_param, "activation": self.activation, "version": self.version})
         if self.dilation != 1:
             json["dilation"] = self.dilation       # (written by dilated blocks only)
+        if self.groups != 1:
+            json["groups"] = self.groups           # (written by grouped blocks only)
         json.update({"layers": [layer.export_json() for layer in self.layers]})
         return json
 

@@ -31,8 +31,15 @@ def layer_geometry(layer):
     """(fwd geometry tuple of ops.conv_geom, human-readable string) of a ConvLayer on its physical NHWC tensors. An anisotropic
     layer (filter, stride or padding per axis): the tuple of ops.conv_rect_geom, 14 long; it runs conv_rect_kernel<pass, BM, BN>.
     A dilated layer: the tuple of ops.conv_dil_geom, 16 long, the dilation named behind the stride (`3x3/1x1 d2x2`); it runs
-    conv_dil_kernel<pass, BM, BN>"""
+    conv_dil_kernel<pass, BM, BN>. A grouped layer: the tuple of ops.conv_grp_geom, 16 long (the window Cw, Kw behind K), the groups
+    named behind the stride (`3x3/1x1 g32`); it runs conv_grp_kernel<pass, BM, BN> on the window's counts"""
     n, _, h, w = layer.input_shape
+    if getattr(layer, "grouped", False):
+        g, _ = ops.conv_grp_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.groups, layer.stride, layer.pad,
+                                 layer.filter_shape[3], layer.ohw)
+        fs = layer.filter_shape
+        return g, "%dx%d %d->%d %dx%d/%dx%d g%d" % ((h, w, fs[1] * layer.groups, fs[0], fs[2], fs[3]) + tuple(layer.stride)
+                                                     + (layer.groups,))
     if getattr(layer, "dilated", False):
         g = ops.conv_dil_geom((n, h, w, layer.cp), layer.omega.dev_shape, layer.stride, layer.pad, layer.dilation,
                               layer.filter_shape[3], layer.ohw)

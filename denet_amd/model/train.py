@@ -223,10 +223,12 @@ def train(args, train_data, log=None, test_data=None):
     skip_train = getattr(args, "skip_train", False)
     set_gradient_norm_args(model, args, log)
     set_ema_args(model, args, log)
-    from ..layer import dilation_log_lines, focal_log_lines
+    from ..layer import dilation_log_lines, focal_log_lines, groups_log_lines
     for line in focal_log_lines(model):      # cost layers with focalGamma > 0 (opt-in)
         log(line)
     for line in dilation_log_lines(model):   # dilated convolutions (`C.D`, dilated blocks; DESIGN.md, "Dilated convolutions")
+        log(line)
+    for line in groups_log_lines(model):     # grouped convolutions (`C.G`, grouped blocks; DESIGN.md, "Grouped convolutions")
         log(line)
     if not skip_train:
         model.build_train_func(args.solver, args.cost_factors)

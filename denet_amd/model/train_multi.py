@@ -78,10 +78,12 @@ def train(args, train_data, dp, log=None):
     train_mod.set_ema_args(model, args, log if dp is None or dp.rank == 0 else None)
     model.ema_auto = not (dp is not None and factor > 1)
     if dp is None or dp.rank == 0:
-        from ..layer import dilation_log_lines, focal_log_lines
+        from ..layer import dilation_log_lines, focal_log_lines, groups_log_lines
         for line in focal_log_lines(model):  # cost layers with focalGamma > 0 (opt-in)
             log(line)
         for line in dilation_log_lines(model):
+            log(line)
+        for line in groups_log_lines(model):
             log(line)
     model.build_train_func(args.solver, args.cost_factors, use_acc_mode=use_acc_mode)
     if dp is not None:

@@ -22,6 +22,12 @@ DENET34_STD_DESC = ("PI[2] C.B[256,3] BNA PI[2] C.B[128,3] BNA DNC[96,100] DNS[7
 # bottleneck) and is consistent with the layer indices denet101.sh:84-90 inserts at (7, 12, 24, 37 after --layer-remove 3)
 RESNET101_DESC = ("C.B[64,7,2] BN A P[3,2,1] nRSN.O[3,256,3,1,64] nRSN.O[4,512,3,2,128] nRSN.O[23,1024,3,2,256] "
                   "nRSN.O[3,2048,3,2,512] P.A[7] R.TB")
+# ResNeXt-50 / -101 32x4d (Xie et al. 2017): the ResNet-50 / -101 block layout with bottlenecks twice as wide whose 3x3 convolution
+# has 32 groups (`nRSN[n, k, size, stride, bottleneck, d, g]`; this build's own grammar, DESIGN.md "Grouped convolutions")
+RESNEXT50_DESC = ("C.B[64,7,2] BN A P[3,2,1] nRSN.O[3,256,3,1,128,1,32] nRSN.O[4,512,3,2,256,1,32] nRSN.O[6,1024,3,2,512,1,32] "
+                  "nRSN.O[3,2048,3,2,1024,1,32] P.A[7] R.TB")
+RESNEXT101_DESC = ("C.B[64,7,2] BN A P[3,2,1] nRSN.O[3,256,3,1,128,1,32] nRSN.O[4,512,3,2,256,1,32] nRSN.O[23,1024,3,2,512,1,32] "
+                   "nRSN.O[3,2048,3,2,1024,1,32] P.A[7] R.TB")
 DENET101_WIDE_DESC = ("PI[2] C[1024,3] SKIP[2] BNA PI[2] C[512,3] SKIP[1] BNA PI[2] C[256,3] SKIP[0] BNA SPLIT DNC[128,200] "
                       "DNS[7,48,0.01,0.1] C.B[2048,1] BNA C.B[1536,1] BNA C.B[1024,1] BNA C.B[768,1] BNA DND[0.5,1,1]")
 DENET101_SKIP_DESC = ("PI[2] C.B[384,3] SKIP[1] BNA PI[2] C.B[192,3] SKIP[0] BNA DNC[128,50] DNS[7,24,0.01,0.1] C.B[2048,1] BNA "
@@ -37,6 +43,19 @@ def resnet34(batch_size, image=224, class_num=1000, seed=1):
     m.batch_size = batch_size
     m.class_num = class_num
     m.build(RESNET34_DESC, (3, image, image), "relu", "half", ["he-backward"])
+    return m
+
+
+def resnext50(batch_size, image=224, class_num=1000, seed=1):
+    """ResNeXt-50 32x4d: the grouped 3x3 layers run conv_grp_kernel (groups of 4, 8, 16 channels on the slab path, of 32 as windows).
+    image: a multiple of 32"""
+    numpy.random.seed(seed)
+    m = model_cnn.ModelCNN()
+    m.batch_size = batch_size
+    m.class_num = class_num
+    # the average pool in front of the head spans the whole last map: 7 x 7 at 224 x 224, image / 32 elsewhere
+    assert image % 32 == 0, "resnext50: the image size must be a multiple of 32 (got %d)" % image
+    m.build(RESNEXT50_DESC.replace("P.A[7]", "P.A[%d]" % (image // 32)), (3, image, image), "relu", "half", ["he-backward"])
     return m
 
 
@@ -63,15 +82,16 @@ def denet34(batch_size, variant="skip", image=512, class_num=80, seed=1, head_de
     return m
 
 
-def denet101(batch_size, variant="wide", image=512, class_num=80, seed=1, head_desc=None):
+def denet101(batch_size, variant="wide", image=512, class_num=80, seed=1, head_desc=None, backbone_desc=None):
     """DeNet-101 <variant> (BASELINE config 5 is `wide`, B=16): the surgery of papers/dss/denet101.sh:82-90,
     head descs :11-21. `wide` taps three scales (256@128^2 via a plain SKIPSRC, 512@64^2, 1024@32^2) and proposes
-    48x48 = 2304 RoIs per image."""
+    48x48 = 2304 RoIs per image. backbone_desc: another backbone of the same 3/4/23/3 block layout, on which the surgery's layer
+    indices stay valid (RESNEXT101_DESC: a DeNet on ResNeXt-101)."""
     numpy.random.seed(seed)
     m = model_cnn.ModelCNN()
     m.batch_size = batch_size
     m.class_num = 1000
-    m.build(RESNET101_DESC, (3, 224, 224), "relu", "half", ["he-backward"])
+    m.build(backbone_desc or RESNET101_DESC, (3, 224, 224), "relu", "half", ["he-backward"])
     m = modify.modify_bn(m, 1, 0.9, 1e-5)
     m = modify.convert_bn_relu(m)
     m = modify.layer_remove(m, 3)

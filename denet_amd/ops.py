@@ -4,6 +4,7 @@ Tensors are NHWC fp32, contiguous, on the current HIP device. No torch arithmeti
 function enqueues hand-written HIP kernels on the current torch stream and returns.
 """
 import contextlib
+import numbers
 import os
 
 import torch
@@ -55,6 +56,8 @@ def kernel_symbol(kind, a, b, c):
         return "conv_rect_kernel<%d, %d, %d>" % (a, b, c)      # pass (0 fwd / 1 dgrad / 2 wgrad), tile BM x BN
     if kind == 25:
         return "conv_dil_kernel<%d, %d, %d>" % (a, b, c)       # the same passes and tiles with dilated taps (`C.D`, `C.DX`)
+    if kind == 26:
+        return "conv_grp_kernel<%d, %d, %d>" % (a, b, c)       # the same passes and tiles on a channel window (`C.G`, `C.GX`)
     if kind == 21:
         return "conv_bf16_kernel<%d, %d>" % (a, b)            # tile BM x BN of the opt-in bf16 kernel (forward, data gradient)
     if kind == 22:
@@ -1503,6 +1506,123 @@ def conv_dil_wgrad(x, dy, w_shape, stride=(1, 1), pad=(0, 0), dilation=(1, 1), s
           "conv_dil_wgrad")
     if PROFILE is not None:
         PROFILE.add(_conv_dil_flops(g, logical))
+    return dw
+
+
+# ---- grouped convolution (csrc/conv_rect.hip, conv_grp_kernel: the same text on a channel window of x, w and y): `C.G` / `C.GX`
+# layers and grouped residual blocks ("Grouped convolutions"). The filter is the compact one, [K][R][S][Cg]. As the
+# rectangular calls: one direct kernel per pass, never in a tuned table, no Winograd, no bf16, no fused statistics.
+GRP_SLAB_SIZES = (1, 2, 4, 8, 16)
+
+
+def conv_grp_window(C, K, groups):
+    """(Cw, Kw, slab) of a grouped layer on C -> K physical channels. Window path: Cg = C / g and Kg = K / g are multiples of 32 and
+    are the window, slab = 0. Slab path: Cg == Kg in GRP_SLAB_SIZES; the window is 32 channels (a slab of 32 / Cg groups) on a filter
+    that is dense inside the slab (denet_conv_grp_expand), slab = Cg. Everything else raises ValueError naming the cause"""
+    if isinstance(groups, bool) or not isinstance(groups, numbers.Integral) or groups < 1:
+        raise ValueError("groups %r: must be an integer >= 1" % (groups,))
+    groups = int(groups)
+    if C % 32 or K % 32:
+        raise ValueError("grouped convolution: %d input and %d output channels - both must be multiples of 32" % (C, K))
+    if C % groups or K % groups:
+        raise ValueError("groups %d does not divide both channel counts (%d input, %d output)" % (groups, C, K))
+    Cg, Kg = C // groups, K // groups
+    if Cg % 32 == 0 and Kg % 32 == 0:
+        return Cg, Kg, 0
+    if Cg == Kg and Cg in GRP_SLAB_SIZES:
+        return 32, 32, Cg
+    raise ValueError("groups %d on %d -> %d channels: unsupported group size (%d input, %d output channels per group) - either both are "
+                     "multiples of 32, or they are equal and one of %s" % (groups, C, K, Cg, Kg, ", ".join(map(str, GRP_SLAB_SIZES))))
+
+
+def conv_grp_geom(x_shape, w_shape, groups, stride, pad, s_real=None, ohw=None):
+    """the geometry tuple of the denet_conv_grp_* calls: (N, H, W, C, K, Cw, Kw, R, S, S_real, sh, sw, ph, pw, OH, OW), and the slab
+    size (0 on the window path). w_shape is the compact filter's, (K, R, S, Cg)"""
+    N, H, W, C = x_shape
+    K, R, S, Cg = w_shape
+    Cw, Kw, slab = conv_grp_window(C, K, groups)
+    assert Cg * int(groups) == C, (x_shape, w_shape, groups)
+    assert s_real is None or s_real == S, (s_real, S)
+    r = conv_rect_geom(x_shape, (K, R, S, C), stride, pad, S, ohw)
+    return r[:5] + (Cw, Kw) + r[5:], slab
+
+
+def _conv_grp_flops(g, groups, logical=None):
+    N, H, W, C, K, Cw, Kw, R, S, s_real, sh, sw, ph, pw, OH, OW = g
+    return 2.0 * N * OH * OW * K * R * S * (C // int(groups))      # the true grouped count: a slab's zeros are not work done
+
+
+def conv_grp_expand(w, Cg, out=None):
+    """the slab filter [K][R][S][32] of the compact filter w [K][R][S][Cg]"""
+    K, R, S, c = w.shape
+    assert c == Cg, (w.shape, Cg)
+    wd = out if out is not None else empty(K, R, S, 32)
+    check(_L().denet_conv_grp_expand(ptr(w), ptr(wd), K, R, S, int(Cg), stream_ptr()), "conv_grp_expand")
+    return wd
+
+
+def conv_grp_compact(dwd, Cg, out=None):
+    """the compact gradient [K][R][S][Cg]: the diagonal blocks of the slab filter's gradient dwd [K][R][S][32]"""
+    K, R, S, c = dwd.shape
+    assert c == 32, dwd.shape
+    dw = out if out is not None else empty(K, R, S, int(Cg))
+    check(_L().denet_conv_grp_compact(ptr(dwd), ptr(dw), K, R, S, int(Cg), stream_ptr()), "conv_grp_compact")
+    return dw
+
+
+def _grp_filter(cache, w, slab):
+    """the filter the kernel reads: w itself on the window path; on the slab path its expansion, made once per weights version and
+    per filter tensor and kept in the layer's cache (as _bf16_filter), so that the forward pass and the data gradient of a step share
+    one expansion and inference expands once. Without a cache: expanded at every call"""
+    if not slab:
+        return w
+    if cache is None:
+        return conv_grp_expand(w, slab)
+    return _bf16_filter(cache, "w_slab", w, lambda f: conv_grp_expand(f, slab))
+
+
+def conv_grp_fwd(x, w, groups, bias=None, add=None, stride=(1, 1), pad=(0, 0), s_real=None, out=None, logical=None, cache=None,
+                 relu=False, ohw=None):
+    x = _settled(x)
+    g, slab = conv_grp_geom(x.shape, w.shape, groups, stride, pad, s_real, ohw)
+    y = out if out is not None else empty(g[0], g[14], g[15], g[4])
+    if cache is not None:
+        cache["bn_stats"] = None               # the batch norm behind measures its own statistics
+    wk = _grp_filter(cache, w, slab)
+    check(_L().denet_conv_grp_fwd(ptr(x), ptr(wk), ptr(bias), ptr(add), ptr(y), int(bool(relu)), *g, stream_ptr()), "conv_grp_fwd")
+    if PROFILE is not None:
+        PROFILE.add(_conv_grp_flops(g, groups, logical))
+    return y
+
+
+def conv_grp_dgrad(dy, w, x_shape, groups, add=None, stride=(1, 1), pad=(0, 0), s_real=None, out=None, logical=None, ohw=None,
+                   cache=None):
+    g, slab = conv_grp_geom(x_shape, w.shape, groups, stride, pad, s_real, ohw)
+    assert tuple(dy.shape) == (g[0], g[14], g[15], g[4]), (dy.shape, g)
+    dx = out if out is not None else empty(*x_shape)
+    wk = _grp_filter(cache, w, slab)
+    check(_L().denet_conv_grp_dgrad(ptr(dy), ptr(wk), ptr(add), ptr(dx), *g, stream_ptr()), "conv_grp_dgrad")
+    if PROFILE is not None:
+        PROFILE.add(_conv_grp_flops(g, groups, logical))
+    return dx
+
+
+def conv_grp_wgrad(x, dy, w_shape, groups, stride=(1, 1), pad=(0, 0), s_real=None, out=None, logical=None, ohw=None):
+    x = _settled(x)
+    g, slab = conv_grp_geom(x.shape, w_shape, groups, stride, pad, s_real, ohw)
+    assert tuple(dy.shape) == (g[0], g[14], g[15], g[4]), (dy.shape, g)
+    dw = out if out is not None else empty(*w_shape)
+    N, H, W, C, K, Cw, Kw, R, S = g[:9]
+    nbytes = int(_L().denet_conv_grp_wgrad_workspace_bytes(N, C, K, Cw, Kw, R, S, g[14], g[15]))
+    ws = WS.get("wgrad_rect", nbytes) if nbytes else None
+    # slab path: the gradient of the dense slab filter goes to scratch, its diagonal blocks are the compact filter's gradient
+    dwk = WS.get("wgrad_grp_slab", K * R * S * 32 * 4).view(torch.float32)[:K * R * S * 32].view(K, R, S, 32) if slab else dw
+    check(_L().denet_conv_grp_wgrad(ptr(x), ptr(dy), ptr(dwk), ptr(ws), ws.numel() if ws is not None else 0, *g, stream_ptr()),
+          "conv_grp_wgrad")
+    if slab:
+        conv_grp_compact(dwk, slab, out=dw)
+    if PROFILE is not None:
+        PROFILE.add(_conv_grp_flops(g, groups, logical))
     return dw
 
 

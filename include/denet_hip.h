@@ -234,6 +234,33 @@ int denet_conv_dil_dgrad(const float* dy, const float* w, const float* add, floa
 int denet_conv_dil_wgrad(const float* x, const float* dy, float* dw_out, float* workspace, size_t workspace_bytes, int N, int H,
                          int W, int C, int K, int R, int S, int S_real, int sh, int sw, int ph, int pw, int dh, int dw, int OH,
                          int OW, hipStream_t stream);
+/* ---- Grouped convolution (csrc/conv_rect.hip, the same kernel text on a channel window of x, w and y): the `C.G[k, size, stride, g]`
+ *      and `C.GX[k, kh, kw, sh, sw, g]` tokens and the grouped residual blocks. The reference has no such parameter; the contract
+ *      is this build's own ("Grouped convolutions"). Arguments as the denet_conv_rect_* twins, with the window (Cw, Kw)
+ *      behind K: the tensors hold C and K channels per pixel, window i (of C / Cw = K / Kw) computes output channels
+ *      [i*Kw, (i+1)*Kw) from input channels [i*Cw, (i+1)*Cw) alone, and the filter is [K][R][S][Cw] correlation taps (bias [K], add
+ *      of the output's shape). Cw and Kw are multiples of 32 that divide C and K into the same number of windows, S_real == S,
+ *      strides are powers of two; anything else returns DENET_ERR_ARG before any device work. The tile is chosen from Cw / Kw, so
+ *      window i computes, bit for bit, what the denet_conv_rect_* twin computes on contiguous copies of that window's channels;
+ *      Cw == C, Kw == K is the twin itself. The filter gradient takes the workspace of denet_conv_grp_wgrad_workspace_bytes (the
+ *      slices of all windows) and is bit-identical from run to run.                                                             */
+int denet_conv_grp_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, int relu, int N, int H,
+                       int W, int C, int K, int Cw, int Kw, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW,
+                       hipStream_t stream);
+int denet_conv_grp_dgrad(const float* dy, const float* w, const float* add, float* dx, int N, int H, int W, int C, int K, int Cw,
+                         int Kw, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH, int OW, hipStream_t stream);
+size_t denet_conv_grp_wgrad_workspace_bytes(int N, int C, int K, int Cw, int Kw, int R, int S, int OH, int OW);
+int denet_conv_grp_wgrad(const float* x, const float* dy, float* dw, float* workspace, size_t workspace_bytes, int N, int H,
+                         int W, int C, int K, int Cw, int Kw, int R, int S, int S_real, int sh, int sw, int ph, int pw, int OH,
+                         int OW, hipStream_t stream);
+/* Groups of Cg = Kg < 32 channels (Cg in {1, 2, 4, 8, 16}; 1 = depthwise) run as windows of 32 channels (slabs) on a filter that
+ * is dense inside a slab. denet_conv_grp_expand writes it from the compact filter w [K][R][S][Cg]:
+ *     wd[k][r][s][j] = w[k][r][s][j % Cg]  if j / Cg == (k % 32) / Cg,  else 0                         (j < 32; wd [K][R][S][32])
+ * denet_conv_grp_compact reads the diagonal blocks of the slab filter's gradient back:
+ *     dw[k][r][s][c] = dwd[k][r][s][((k % 32) / Cg) * Cg + c]                                         (c < Cg; dw [K][R][S][Cg])
+ * K is a multiple of 32. Plain stores, no atomics: both are exact and bit-identical from run to run.                             */
+int denet_conv_grp_expand(const float* w, float* wd, int K, int R, int S, int Cg, hipStream_t stream);
+int denet_conv_grp_compact(const float* dwd, float* dw, int K, int R, int S, int Cg, hipStream_t stream);
 /* ---- OPT-IN bf16 inference (csrc/conv_bf16.hip), never the fp32 path and never taken by training: the forward pass of a square
  *      convolution (geometry and tensors as denet_conv_fwd_act; C % 32 = 0, every tap real) with both operands rounded to bf16,
  *          y = epilogue( sum over taps and channels of bf16(x) * bf16(w) ),  accumulated in fp32 (v_mfma_f32_32x32x16_bf16).
