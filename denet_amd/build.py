@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libdenet_hip.so")
 
 SOURCES = ["runtime.hip", "igemm.hip", "bn.hip", "pool.hip", "elementwise.hip", "dss.hip", "samples.hip", "detect.hip", "winograd.hip", "wino2f.hip", "wino4f.hip", "wino4t.hip", "dgrad_s2.hip", "wino4g.hip", "stem.hip", "gemm3b.hip", "bn_moments.hip",
-           "regression.hip", "augment.hip", "image.hip", "activation.hip", "conv_rect.hip", "pool_border.hip", "conv_bf16.hip", "conv_bf16_train.hip", "cluster.hip", "bn_renorm.hip", "grad_norm.hip", "sparse_bilinear.hip", "focal.hip", "ema.hip"]
+           "regression.hip", "augment.hip", "image.hip", "activation.hip", "conv_rect.hip", "pool_border.hip", "conv_bf16.hip", "conv_bf16_train.hip", "cluster.hip", "bn_renorm.hip", "grad_norm.hip", "sparse_bilinear.hip", "focal.hip", "ema.hip", "gn.hip"]
 # files whose integer results must not depend on FMA contraction (focal.hip: its box and fitness terms must give dss.hip's bits)
 NO_CONTRACT = {"dss.hip", "samples.hip", "detect.hip", "augment.hip", "image.hip", "cluster.hip", "sparse_bilinear.hip", "focal.hip"}
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -3,7 +3,10 @@ cuDNN batch statistics (biased variance, eps inside the sqrt), running `mean` an
 deviation `stdinv` with momentum (:75-76), gamma/beta reported as biases (no L2 decay, :106-107), and the
 test-time path that feeds var = 1/stdinv^2 to cuDNN which adds eps a second time (:50-52).
 The batch renormalisation the reference keeps commented out (:65-73) runs here for the layers whose parameters ask for it
-(renormMaxR > 1 or renormMaxD > 0): ops.bn_renorm_fwd_train / bn_renorm_bwd, DESIGN.md section 14."""
+(renormMaxR > 1 or renormMaxD > 0): ops.bn_renorm_fwd_train / bn_renorm_bwd, DESIGN.md section 14.
+GROUP NORMALISATION (Wu & He 2018) is a mode of the same layers, this build's own (`BN.G[g, eps]`, `BNA.G[g, eps]`, the JSON key
+normGroups): per-sample statistics over g groups of consecutive channels, identical in training and
+inference (ops.gn_fwd / gn_bwd, csrc/gn.hip). `mean` / `stdinv` / `momentum` stay in the layer and in the file, unread."""
 import math
 
 import numpy
@@ -57,12 +60,47 @@ def renorm_log_line(model, epoch):
         len(ls), epoch, " ".join("r_max=%.6g d_max=%.6g" % lim for lim in lims))
 
 
+def norm_groups_check(groups, channels=None, what="batch norm"):
+    """refuses a normGroups value no layer could run with, when the layer is built; 0 = batch statistics (the mode is off)"""
+    if isinstance(groups, (float, numpy.floating)) and float(groups).is_integer():
+        groups = int(groups)          # (the desc grammar and JSON hand numbers over as they were written: `8.0` is 8)
+    if isinstance(groups, bool) or not isinstance(groups, (int, numpy.integer)) or groups < 0:
+        raise ValueError("%s: normGroups must be an integer >= 1 (0 in a model file: batch statistics), got %r" % (what, groups))
+    groups = int(groups)
+    if groups and channels is not None and channels % groups:
+        raise ValueError("%s: normGroups %d does not divide the layer's %d channels" % (what, groups, channels))
+    return groups
+
+
+def desc_norm_groups(params):
+    """g of a `BN.G[g, eps]` / `BNA.G[g, eps]` token (default 32). The token asks for the mode, so 0 - which in a model file
+    means batch statistics - is refused here like every other value that is no integer >= 1"""
+    g = params.get(0, 32)
+    if not isinstance(g, bool) and g == 0:
+        raise ValueError("batch norm: normGroups must be an integer >= 1 in a `.G[g, eps]` token, got %r" % (g,))
+    return g
+
+
+def group_norm_layers(model):
+    """the batch-norm layers of a model that run as group norms, nested ones included"""
+    from ..model.model_cnn import walk_layers
+    return [l for l in walk_layers(model.layers) if isinstance(l, BatchNormLayer) and l.enabled and l.norm_groups]
+
+
+def group_norm_log_line(model):
+    """what model-train reports once at start, or None for a model without group-mode layers"""
+    ls = group_norm_layers(model)
+    if not ls:
+        return None
+    return "group norm: %d layers, groups %s" % (len(ls), " ".join(str(g) for g in sorted({l.norm_groups for l in ls})))
+
+
 class BatchNormLayer(AbstractLayer):
     type_name = "batchnorm"
     fused_relu = False
 
     def __init__(self, layers, momentum=0.9, eps=1e-5, renorm_max_r=1.0, renorm_max_d=0.0, renorm_max_it=10,
-                 json_param={}):
+                 json_param={}, norm_groups=0):
         super().__init__(layer_index=len(layers))
         self.input = layers[-1].output
         self.input_shape = layers[-1].output_shape
@@ -76,6 +114,18 @@ class BatchNormLayer(AbstractLayer):
         # renorm-active layers take a route of their own in training (csrc/bn_renorm.hip) and give up every fusion
         self.renorm_active = renorm_active(self.renorm_max_r, self.renorm_max_d)
         self.output_shape = self.input_shape
+        # group normalisation: normGroups > 0 groups of consecutive channels, statistics per sample. Like a
+        # renorm-active layer it takes a route of its own (csrc/gn.hip) and gives up every batch-norm fusion
+        what = "batch norm layer %d" % self.layer_index
+        self.norm_groups = norm_groups_check(json_param.get("normGroups", norm_groups), what=what)
+        if self.norm_groups:
+            if self.renorm_active:
+                raise ValueError("%s: normGroups %d together with an active batch renormalisation (renormMaxR %r, renormMaxD %r) - "
+                                 "a group norm has no batch statistics to correct" % (what, self.norm_groups, self.renorm_max_r,
+                                                                                     self.renorm_max_d))
+            if not self.enabled:
+                raise ValueError("%s: normGroups %d on a layer with enabled false" % (what, self.norm_groups))
+            norm_groups_check(self.norm_groups, self.input_shape[1], what)
         if self.enabled:
             assert self.input.cp == self.input_shape[1], "batch norm needs an unpadded channel count (multiple of 32)"
             c = self.input_shape[1]
@@ -84,8 +134,9 @@ class BatchNormLayer(AbstractLayer):
             self.mean = Param(numpy.zeros((c,)), "bn mean")
             self.stdinv = Param(numpy.ones((c,)), "bn std inv")
             self.output = Act(self.output_shape, self.input.cp, "bn%i" % self.layer_index)
-            self.input.want_stats = True      # a convolution writing this tensor also emits its per-channel sums
-            self.input.stats_bn = self        # ... and may finish this layer's statistics in its own launch (ops.BnFinal)
+            if not self.norm_groups:
+                self.input.want_stats = True      # a convolution writing this tensor also emits its per-channel sums
+                self.input.stats_bn = self        # ... and may finish this layer's statistics in its own launch (ops.BnFinal)
         else:
             self.output = self.input
         self._save = None
@@ -94,6 +145,10 @@ class BatchNormLayer(AbstractLayer):
     def parse_desc(layers, name, tags, params):
         if name != "BN":
             return False
+        if "G" in tags:
+            # `BN.G[g, eps]`: the tag changes what the positional parameters mean (as on `C.G`); momentum keeps its default, unread
+            layers.append(BatchNormLayer(layers, eps=params.get(1, 1e-5), norm_groups=desc_norm_groups(params)))
+            return True
         layers.append(BatchNormLayer(layers, params.get(0, 0.9), params.get(1, 1e-5), params.get(2, 1),
                                      params.get(3, 0), params.get(4, 0)))
         return True
@@ -122,6 +177,8 @@ class BatchNormLayer(AbstractLayer):
                      "renormMaxD": self.renorm_max_d,
                      "renormMaxIt": self.renorm_max_it,
                      "enabled": self.enabled})
+        if self.norm_groups:
+            json["normGroups"] = self.norm_groups      # (written by group-mode layers only: default files keep their keys)
         return json
 
     def import_json(self, json_param):
@@ -135,7 +192,7 @@ class BatchNormLayer(AbstractLayer):
     def stats_final(self, act):
         """for the convolution pass that writes `act` (this layer's input) in a training step: the description of this layer's
         statistics, so that the pass can finish them in its own launch (ops.BnFinal; the running statistics are updated there)"""
-        if not (self.enabled and ops.FINAL_FOLD and act is self.input) or self.renorm_active:
+        if not (self.enabled and ops.FINAL_FOLD and act is self.input) or self.renorm_active or self.norm_groups:
             return None
         if getattr(self, "pool_behind", None) is not None and ops.BN_POOL_FUSE:
             # the fused BN + ReLU + max-pool pass reduces the partial rows itself and updates the running statistics there
@@ -158,6 +215,16 @@ class BatchNormLayer(AbstractLayer):
         relu = self.fused_relu if relu is None else relu
         out_act = self.output if out_act is None else out_act
         x = self.input.data
+        if self.norm_groups:
+            # group normalisation: one route for training and inference, no batch statistics, no BnLink, no pool fusion (the pool
+            # runs behind it); the running statistics are neither read nor written
+            train = bool(get_train())
+            y, sm, si = ops.gn_fwd(x, self.omega.dev, self.beta.dev, self.norm_groups, self.eps, relu=relu, res=res, save=train)
+            if train:
+                self._save = (sm, si, relu, out_act, res is not None)
+                self._pooled = False
+            out_act.data = y
+            return
         if get_train():
             # per-channel sums already written by the convolution that produced x (ConvLayer.forward), valid for this tensor only
             pre = getattr(self.input, "stats", None)
@@ -219,7 +286,7 @@ class BatchNormLayer(AbstractLayer):
     def sums_request(self, act):
         """for the data-gradient pass that writes the gradient of `act` (this layer's output of the current training step): the
         description of this batch norm, so that the pass leaves the two backward reductions behind (ops.BnSums)"""
-        if not (self.enabled and self._save is not None) or self.renorm_active:
+        if not (self.enabled and self._save is not None) or self.renorm_active or self.norm_groups:
             return None
         if getattr(self, "_pooled", False):
             # the fused BN + ReLU + max pool: `act` is the POOL's output; over the pooled tensors the layer looks like a batch norm
@@ -244,6 +311,12 @@ class BatchNormLayer(AbstractLayer):
         if not self.enabled:
             return None
         sm, si, relu, out_act, has_res = self._save
+        if self.norm_groups:
+            y = out_act.data if (relu and has_res) else None      # (no residual: the mask is recomputed from x)
+            dx, dres, _, _ = ops.gn_bwd(self.input.data, y, out_act.grad, self.omega.dev, sm, si, self.norm_groups, relu=relu,
+                                        want_dres=want_dres, dgamma=self.omega.grad, dbeta=self.beta.grad, beta=self.beta.dev)
+            self.input.add_grad(dx)
+            return dres
         if self.renorm_active:
             y = out_act.data if (relu and has_res) else None      # (no residual: the mask is recomputed from x, as in the forward)
             dx, dres, _, _ = ops.bn_renorm_bwd(self.input.data, y, out_act.grad, sm, si, self._renorm_state, relu=relu,

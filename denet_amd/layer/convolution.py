@@ -388,6 +388,7 @@ class ConvLayer(AbstractLayer):
     def forward_folded(self, ctx, bn, add=None, relu=False, out_act=None):
         """inference only: this convolution with the batch-norm layer behind it folded into its filters (recomputed
         when the weights change), residual `add` and ReLU in the epilogue; writes the batch norm's output"""
+        assert not getattr(bn, "norm_groups", 0), "a group-mode norm cannot be folded into the convolution in front of it"
         cache = self._cache()
         self._record_mode(cache, False)
         ent = cache.get("fold")

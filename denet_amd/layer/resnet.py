@@ -183,8 +183,8 @@ class ResnetLayer(AbstractLayer):
             out, i = [], 0
             while i < len(ls):
                 if ls[i].type_name != "conv" or i + 1 >= len(ls) or ls[i + 1].type_name not in ("batchnorm", "batchnorm-relu") \
-                        or not ls[i].enabled or not ls[i + 1].enabled:
-                    return None
+                        or not ls[i].enabled or not ls[i + 1].enabled or ls[i + 1].norm_groups:
+                    return None                # (group-mode norms are per sample: nothing to fold into the filters)
                 bn = ls[i + 1]
                 if getattr(bn, "act_fused", False) and i + 2 < len(ls) and ls[i + 2] is bn.act_behind:
                     out.append((ls[i], bn, True, bn.act_behind.output))       # `BN A`: the folded pass writes the activation's output

@@ -395,6 +395,9 @@ class ModelCNN:
             if a.type_name == "batchnorm" and getattr(a, "act_fused", False) and a.act_behind is act and b.type_name == "pool" \
                     and b.mode == "max" and b.ignore_border and b.input is act.output and self._consumers(act.output) == 1:
                 a.pool_behind = b
+        for a in self.layers:
+            if getattr(a, "norm_groups", 0):
+                a.pool_behind = None           # a group-mode layer has no pooled form: the pool runs behind it
         # a SKIP layer that adds its tap (same channel count: no projection) to the output of the convolution right in front of it
         # (the up-sampling path of the skip models, skip.py:81-86): the addition goes into that convolution's epilogue, and with it the statistics of the batch
         # norm behind the SKIP layer - no pass of its own over the sum (DENET_SKIP_FUSE=0: separate passes)
@@ -472,7 +475,8 @@ class ModelCNN:
             if fold and layer.type_name == "conv" and layer.enabled and i + 2 < len(self.layers):
                 nxt = self.layers[i + 2]
                 if nxt.type_name in ("batchnorm", "batchnorm-relu") and nxt.enabled and nxt.input is layer.output \
-                        and self._consumers(layer.output) == 1:
+                        and not nxt.norm_groups and self._consumers(layer.output) == 1:
+                    # (a group-mode layer has no per-channel statistics to fold: the convolution runs with its own bias or none)
                     # folded only when the batch norm is the ONLY reader of the convolution's output: the folded pass
                     # writes normalised values into it, any other consumer (skip source, split, detection tail) needs the raw ones
                     act = nxt.act_behind if getattr(nxt, "act_fused", False) else None      # `BN A` as one pass: ActivationLayer

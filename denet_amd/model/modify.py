@@ -2,7 +2,9 @@
 classifier: --class-num, --image-size, --use-cudnn-pool (:62-68), --convert-bn-relu (:76-113), --modify-bn (:115-131), --layer-remove
 (:153-156), --layer-insert N:DESC (:161-175), --layer-append (:177-184). Like the reference every edit goes
 through the JSON form and a reload, so shapes and wiring are rebuilt from scratch. --modify-bn-renorm R D IT is this build's
-own: the switch for the batch renormalisation the reference carries parameters for and keeps commented out (batch_norm.py:65-73)."""
+own: the switch for the batch renormalisation the reference carries parameters for and keeps commented out (batch_norm.py:65-73).
+So is --modify-bn-groups G: the same traversal sets the key normGroups, which runs the batch norms as group norms (DESIGN.md
+section 21)."""
 import copy
 
 from . import model_cnn
@@ -48,6 +50,8 @@ def _bn_to_bnrelu(bn_json):
         for k in RENORM_KEYS:          # a renorm-active layer stays one (the fused layer writes the keys only then)
             if k in bn_json:
                 out[k] = bn_json[k]
+    if bn_json.get("normGroups", 0):
+        out["normGroups"] = bn_json["normGroups"]      # a group-mode layer stays one
     return out
 
 
@@ -84,6 +88,41 @@ def modify_bn_renorm(model, max_r, max_d, max_it):
             for s in l["layers"]:
                 if s["type"] in ("batchnorm", "batchnorm-relu"):
                     edit(s, False)
+    return _reload(model, j)
+
+
+def modify_bn_groups(model, groups):
+    """--modify-bn-groups G: group normalisation for every batchnorm and batchnorm-relu layer and the bnParam
+    of every residual block, where it reaches every norm of the block; modify_bn_renorm's traversal. 0 goes back to batch
+    statistics: the key leaves every place (it is written only when it is not 0). Refuses, naming the layer, when G does not
+    divide a layer's channel count"""
+    from ..layer.batch_norm import BatchNormLayer, norm_groups_check
+    groups = norm_groups_check(groups, what="--modify-bn-groups")
+    if groups:
+        for l in model_cnn.walk_layers(model.layers):
+            if isinstance(l, BatchNormLayer) and l.enabled and l.input_shape[1] % groups:
+                raise ValueError("--modify-bn-groups %d: layer %d (%s%s) has %d channels, which %d does not divide"
+                                 % (groups, l.layer_index, l.type_name, "" if l in model.layers else ", inside a residual block",
+                                    l.input_shape[1], groups))
+
+    def edit(d):
+        if groups:
+            d["normGroups"] = groups
+        else:
+            d.pop("normGroups", None)
+
+    j = model.export_json()
+    for l in j["layers"]:
+        if l["type"] in ("batchnorm", "batchnorm-relu"):
+            if l.get("enabled", True):
+                edit(l)
+        elif l["type"] == "resnet":
+            l["bnParam"] = dict(l.get("bnParam", {}))
+            if l["bnParam"].get("enabled", True):
+                edit(l["bnParam"])
+            for s in l["layers"]:
+                if s["type"] in ("batchnorm", "batchnorm-relu") and s.get("enabled", True):
+                    edit(s)
     return _reload(model, j)
 
 
@@ -253,6 +292,9 @@ def build_parser():
                         help="batch renormalisation for every batch norm (training only): r is clipped to [1/R, R], d to [-D, D], the "
                              "limits open over the first IT epochs (0: open from the start); 1 0 0 switches it off (a top-level batchnorm "
                              "layer then carries renormMaxIt 0, whatever it carried before)")
+    parser.add_argument("--modify-bn-groups", default=None, type=int, metavar="G",
+                        help="group normalisation for every batch norm (training and inference): statistics per sample over G groups "
+                             "of consecutive channels; G must divide every layer's channel count; 0 goes back to batch statistics")
     parser.add_argument("--modify-layer", default=None, nargs="+", type=str, help="TYPE key=value ...")
     parser.add_argument("--layer-insert", default=[], nargs="+", help="insert layer at position N:DESC")
     parser.add_argument("--layer-remove", default=0, type=int, help="remove N layer from end")
@@ -280,6 +322,8 @@ def main(argv=None):
         model = modify_bn(model, bool(args.modify_bn[0]), float(args.modify_bn[1]), float(args.modify_bn[2]))
     if args.modify_bn_renorm is not None:
         model = modify_bn_renorm(model, *args.modify_bn_renorm)
+    if args.modify_bn_groups is not None:
+        model = modify_bn_groups(model, args.modify_bn_groups)
     if args.convert_bn_relu:
         model = convert_bn_relu(model)
     model = layer_remove(model, args.layer_remove)

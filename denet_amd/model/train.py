@@ -239,7 +239,10 @@ def train(args, train_data, log=None, test_data=None):
         from ..dataset.device_render import DeviceImageLoader
         device_loader = DeviceImageLoader(max(1, getattr(args, "thread_num", 1)), True, cp=model.input.cp, decode="process",
                                           params=train_data.image_loader)
-    from ..layer.batch_norm import renorm_log_line
+    from ..layer.batch_norm import group_norm_log_line, renorm_log_line
+    gn_line = group_norm_log_line(model)
+    if gn_line is not None:
+        log(gn_line)                     # batch norms in group mode (`BN.G`, normGroups), once at start
     for epoch in range(args.epochs):
         renorm = None if skip_train else renorm_log_line(model, epoch)
         if renorm is not None:

@@ -104,7 +104,10 @@ def train(args, train_data, dp, log=None):
     for epoch in range(0, epoch_start):                 # train_multi.py:406-410
         if len(args.learn_anneal_epochs) == 0 or (epoch + 1) in args.learn_anneal_epochs:
             learn_rate *= args.learn_anneal
-    from ..layer.batch_norm import renorm_log_line
+    from ..layer.batch_norm import group_norm_log_line, renorm_log_line
+    gn_line = group_norm_log_line(model) if rank == 0 else None
+    if gn_line is not None:
+        log(gn_line + " (per sample: no statistics to synchronise)")
     for epoch in range(epoch_start, args.epochs):
         renorm = renorm_log_line(model, epoch) if rank == 0 else None
         if renorm is not None:

@@ -3,7 +3,8 @@ test-mode activations, leaving every other parameter as it is. Mirrors denet/mod
 
   1. the layers (:44-51): top-level `batchnorm` / `batchnorm-relu` layers and those among the `layers` of each `resnet`, in
      model order, each resnet's in its stored order; batch norms nested anywhere else are not touched (they are logged), nor
-     are disabled ones (they have no statistics);
+     are disabled ones (they have no statistics) or layers in group mode (normGroups > 0: per-sample statistics, nothing stored;
+     they are logged as skipped, and a model with no other batch norm is written back unchanged);
   2. sequential (:53-60): layer i is estimated from test-mode forward passes in which every batch norm in front of it
      normalises with its stored statistics, those of the layers < i already being the new ones; the pass records the
      per-channel mean and biased variance of the RAW input of layer i;
@@ -43,7 +44,8 @@ def _select(model):
             chosen.append((layer, layer))
         elif layer.type_name == "resnet":
             chosen += [(l, layer) for l in layer.layers if l.type_name in BN_TYPES]
-    chosen = [(l, top) for l, top in chosen if l.enabled]
+    # (a group-mode layer - normGroups > 0, DESIGN.md section 21 - has no running statistics to estimate: left out, and logged)
+    chosen = [(l, top) for l, top in chosen if l.enabled and not l.norm_groups]
     ids = set(id(l) for l, _ in chosen)
     skipped = [l for l in walk_layers(model.layers) if l.type_name in BN_TYPES and id(l) not in ids]
     return chosen, skipped
@@ -66,7 +68,12 @@ def update_bn(model, batches, log=None, device_budget=DEVICE_BUDGET):
     chosen, skipped = _select(model)
     log("Found %i batch norm layers" % len(chosen))
     for l in skipped:
-        log("Skipping batch norm layer %i (%s)" % (l.layer_index, "disabled" if not l.enabled else "not top-level or in a resnet"))
+        log("Skipping batch norm layer %i (%s)" % (l.layer_index, "disabled" if not l.enabled else
+                                                    "group norm, %d groups: no running statistics" % l.norm_groups if l.norm_groups
+                                                    else "not top-level or in a resnet"))
+    if not chosen:
+        log("No batch norm layer with running statistics: nothing to estimate, the model is left unchanged")
+        return []
     if not model._packed:
         model.pack_device()
     nbytes = sum(int(numpy.prod(b.shape)) * 4 for b in batches)

@@ -37,6 +37,12 @@ SIMPLE_CIFAR10_DESC = ("B[3] C[128,3] BN A C[96,2] BN A C[64,1] BN A P.A[2] D[0.
                        "P.A[2] D[0.2] C[512,3] BN A C[384,2] BN A C[256,1] BN A D[0.2] R.C[6]")
 
 
+def _norm_groups(m, norm_groups):
+    """norm_groups > 0: every batch norm of the built model runs as a group norm (model-modify --modify-bn-groups; DESIGN.md section
+    21). 0, the default: the model as it always was"""
+    return modify.modify_bn_groups(m, norm_groups) if norm_groups else m
+
+
 def resnet34(batch_size, image=224, class_num=1000, seed=1):
     numpy.random.seed(seed)
     m = model_cnn.ModelCNN()
@@ -46,7 +52,7 @@ def resnet34(batch_size, image=224, class_num=1000, seed=1):
     return m
 
 
-def resnext50(batch_size, image=224, class_num=1000, seed=1):
+def resnext50(batch_size, image=224, class_num=1000, seed=1, norm_groups=0):
     """ResNeXt-50 32x4d: the grouped 3x3 layers run conv_grp_kernel (groups of 4, 8, 16 channels on the slab path, of 32 as windows).
     image: a multiple of 32"""
     numpy.random.seed(seed)
@@ -56,10 +62,10 @@ def resnext50(batch_size, image=224, class_num=1000, seed=1):
     # the average pool in front of the head spans the whole last map: 7 x 7 at 224 x 224, image / 32 elsewhere
     assert image % 32 == 0, "resnext50: the image size must be a multiple of 32 (got %d)" % image
     m.build(RESNEXT50_DESC.replace("P.A[7]", "P.A[%d]" % (image // 32)), (3, image, image), "relu", "half", ["he-backward"])
-    return m
+    return _norm_groups(m, norm_groups)
 
 
-def denet34(batch_size, variant="skip", image=512, class_num=80, seed=1, head_desc=None):
+def denet34(batch_size, variant="skip", image=512, class_num=80, seed=1, head_desc=None, norm_groups=0):
     """DeNet-34 <variant> built through the same surgery as papers/dss/denet34.sh:83-96"""
     numpy.random.seed(seed)
     m = model_cnn.ModelCNN()
@@ -79,10 +85,10 @@ def denet34(batch_size, variant="skip", image=512, class_num=80, seed=1, head_de
     else:
         raise Exception("unknown DeNet-34 variant " + variant)
     m = modify.layer_append(m, head_desc or desc)
-    return m
+    return _norm_groups(m, norm_groups)
 
 
-def denet101(batch_size, variant="wide", image=512, class_num=80, seed=1, head_desc=None, backbone_desc=None):
+def denet101(batch_size, variant="wide", image=512, class_num=80, seed=1, head_desc=None, backbone_desc=None, norm_groups=0):
     """DeNet-101 <variant> (BASELINE config 5 is `wide`, B=16): the surgery of papers/dss/denet101.sh:82-90,
     head descs :11-21. `wide` taps three scales (256@128^2 via a plain SKIPSRC, 512@64^2, 1024@32^2) and proposes
     48x48 = 2304 RoIs per image. backbone_desc: another backbone of the same 3/4/23/3 block layout, on which the surgery's layer
@@ -106,7 +112,7 @@ def denet101(batch_size, variant="wide", image=512, class_num=80, seed=1, head_d
     else:
         raise Exception("unknown DeNet-101 variant " + variant)
     m = modify.layer_append(m, head_desc or desc)
-    return m
+    return _norm_groups(m, norm_groups)
 
 
 def cifar3(batch_size=32, class_num=10, seed=1):

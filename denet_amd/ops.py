@@ -65,6 +65,8 @@ def kernel_symbol(kind, a, b, c):
     fixed = {11: "wino2f_wgrad_kernel", 12: "stem_fwd_kernel", 13: "stem_wgrad_kernel", 23: "conv_bf16_wgrad_reduce_kernel",
              24: "filter_to_bf16_dgrad_kernel", 30: "cluster_init_kernel", 31: "cluster_pairs_kernel", 32: "cluster_label_kernel",
              33: "cluster_select_kernel", 40: "bn_renorm_stats_finish_kernel", 41: "bn_renorm_grad_fold_kernel",
+             42: "gn_stats_partial_kernel", 43: "gn_stats_finish_kernel", 44: "gn_apply_kernel", 45: "gn_bwd_partial_kernel",
+             46: "gn_bwd_finish_kernel", 47: "gn_bwd_apply_kernel",
              50: "grad_norm_partial_kernel", 51: "grad_norm_finish_kernel", 52: "solver_coef_kernel", 53: "adam_coef_kernel",
              54: "ema_update_kernel", 55: "swap_kernel",
              60: "sparse_bilinear_fwd_kernel", 61: "sparse_bilinear_bwd_kernel",
@@ -2093,6 +2095,56 @@ def bn_renorm_bwd(x, y, dy, save_mean, save_invstd, state, relu=False, want_dres
                                    ptr(dgamma), ptr(dbeta), ptr(ws), M, C, int(relu), stream_ptr()), "bn_renorm_bwd")
     if PROFILE is not None:
         PROFILE.add(0.0)                   # (the record of the gradient-fold launch)
+    return dx, dres, dgamma, dbeta
+
+
+# ---- group normalisation (csrc/gn.hip; no reference counterpart) ----
+GN_FWD_KERNELS = ("gn_stats_partial_kernel", "gn_stats_finish_kernel", "gn_apply_kernel")      # what a group-mode layer runs forward
+GN_BWD_KERNELS = ("gn_bwd_partial_kernel", "gn_bwd_finish_kernel", "gn_bwd_apply_kernel")     # ... and backward
+GN_KERNELS = GN_FWD_KERNELS + GN_BWD_KERNELS
+
+
+def _gn_shape(x, groups):
+    C = x.shape[-1]
+    N = x.shape[0]
+    HW = x.numel() // (N * C)
+    groups = int(groups)
+    assert groups >= 1 and C % groups == 0, "group norm: %d groups do not divide %d channels" % (groups, C)
+    return N, HW, C, groups
+
+
+def gn_fwd(x, gamma, beta, groups, eps=1e-5, relu=False, res=None, out=None, save=True):
+    """group normalisation of x [N, ..., C] over `groups` groups of consecutive channels, per sample: y = (x - mu) * inv * gamma +
+    beta [+ res] [relu], the same in training and inference. Returns (y, save_mean, save_invstd), the statistics [N, groups]
+    (save=False - inference - keeps them in the workspace and returns None for both)"""
+    N, HW, C, G = _gn_shape(x, groups)
+    y = out if out is not None else torch.empty_like(x)
+    save_mean, save_invstd = (empty(N, G), empty(N, G)) if save else (None, None)
+    ws = WS.get("gn", _L().denet_gn_workspace_bytes(N, HW, C))
+    check(_L().denet_gn_fwd(ptr(x), ptr(res), ptr(y), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), ptr(ws), N, HW, C, G,
+                            float(eps), int(relu), stream_ptr()), "gn_fwd")
+    if PROFILE is not None:
+        for _ in GN_FWD_KERNELS:
+            PROFILE.add(0.0)               # (the records of the three launches)
+    return y, save_mean, save_invstd
+
+
+def gn_bwd(x, y, dy, gamma, save_mean, save_invstd, groups, relu=False, want_dres=False, dgamma=None, dbeta=None, beta=None,
+           dx=None):
+    """gradient of gn_fwd: dx = inv * (gamma * g - S1 / m - xhat * S2 / m), dres = g, dgamma / dbeta WRITTEN (as bn_bwd: the given
+    tensors are overwritten, not accumulated into). y may be None for a relu layer without residual when beta is given: the mask is
+    recomputed from x. Returns (dx, dres, dgamma, dbeta)"""
+    N, HW, C, G = _gn_shape(x, groups)
+    dx = dx if dx is not None else torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    dgamma = dgamma if dgamma is not None else empty(C)
+    dbeta = dbeta if dbeta is not None else empty(C)
+    ws = WS.get("gn", _L().denet_gn_workspace_bytes(N, HW, C))
+    check(_L().denet_gn_bwd(ptr(x), ptr(y), ptr(dy), ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), ptr(dx), ptr(dres),
+                            ptr(dgamma), ptr(dbeta), ptr(ws), N, HW, C, G, int(relu), stream_ptr()), "gn_bwd")
+    if PROFILE is not None:
+        for _ in GN_BWD_KERNELS:
+            PROFILE.add(0.0)
     return dx, dres, dgamma, dbeta
 
 

@@ -546,6 +546,29 @@ int denet_bn_renorm_fwd_train(const float* x, const float* res, float* y, const 
 int denet_bn_renorm_bwd(const float* x, const float* y, const float* dy, const float* save_mean, const float* save_invstd,
                         const float* state, float* dx, float* dres, float* dgamma, float* dbeta, void* workspace, long M, int C,
                         int relu, hipStream_t stream);
+/* Group normalisation (Wu & He 2018; no reference counterpart - csrc/gn.hip), the mode of the batch-norm
+ * layers with normGroups > 0. x, res, y, dy, dx, dres: NHWC [N][HW][C]; G groups of Cg = C / G consecutive channels (C a multiple
+ * of 4 and of G), m = HW * Cg. Per sample n and group j, the same in training and inference (no running statistics):
+ *   mu = sum x / m, inv = 1 / sqrt(sum (x - mu)^2 / m + eps),  y = (x - mu) * (inv * gamma[c]) + beta[c] [+ res] [relu]
+ * Every sum is accumulated in double in a fixed order, no atomics: two runs give the same bits, and the order of a sample depends
+ * on (HW, C, G) only, so y[n], dx[n] and the saved statistics of a sample do not depend on N or on its position in the batch. A
+ * group with m = 1 gives y == beta (+ res, relu) and dx == 0 exactly.
+ *   denet_gn_workspace_bytes: the scratch both calls need (per-sample partial sums [N][rows][2][C] doubles + small per-group vectors).
+ *   denet_gn_fwd: three launches - per-sample column sums of x and x^2 with a sample's rows split over many workgroups
+ *              (gn_stats_partial_kernel), one wave per (n, j) that folds rows and channels into save_mean / save_invstd [N * G]
+ *              (gn_stats_finish_kernel), the pointwise pass (gn_apply_kernel). res: NULL or the residual added before the ReLU.
+ *              save_mean / save_invstd: both NULL (inference) keeps the statistics in the workspace.
+ *   denet_gn_bwd: with g = dy masked by the ReLU (from y when given - a residual was added - else recomputed from x, which needs
+ *              beta) and xhat = (x - mu) * inv: per-sample column sums A = sum g, B = sum g * xhat (gn_bwd_partial_kernel); one launch
+ *              (gn_bwd_finish_kernel) leaves S1 = sum_{c in j} gamma A and S2 = sum_{c in j} gamma B per (n, j) and WRITES (overwrites,
+ *              never accumulates into - as denet_bn_bwd) dgamma[c] = sum_n B and dbeta[c] = sum_n A, the samples added in ascending
+ *              order; then dx = inv * (gamma * g - S1 / m - xhat * S2 / m), dres (optional) = g (gn_bwd_apply_kernel). */
+size_t denet_gn_workspace_bytes(int N, long HW, int C);
+int denet_gn_fwd(const float* x, const float* res, float* y, const float* gamma, const float* beta, float* save_mean,
+                 float* save_invstd, void* workspace, int N, long HW, int C, int G, float eps, int relu, hipStream_t stream);
+int denet_gn_bwd(const float* x, const float* y, const float* dy, const float* gamma, const float* beta, const float* save_mean,
+                 const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, void* workspace, int N, long HW,
+                 int C, int G, int relu, hipStream_t stream);
 /* A max pool directly behind a BN + ReLU layer (batch_norm_relu.py:34-48 -> pool.py:38, the ResNet stem), training: the
  * normalised tensor is never written. Forward: statistics from `partial` / `rows` (denet_conv_fwd_stats) or, partial = NULL,
  * measured here (workspace = denet_bn_workspace_bytes(N*H*W, C)); writes y_pool [N,OH,OW,C] and the argmax taps (first maximum
